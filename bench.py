@@ -9,6 +9,11 @@ host batch synthesis (native dummy-QA generator, pinned) → H2D → fused BERT-
 5-way QA loss → backward with bucketed RCCL all-reduce overlapped → on-device grad-norm clip →
 fused AdamW → LR schedule.  Weak scaling: ``--batch`` samples per GPU per step.
 Rank 0 prints ONE JSON line; ``value`` is the whole-job aggregate (max elapsed over ranks).
+
+A plain run does only what that line needs: set-up, ``--warmup`` untimed steps, ``--steps`` timed steps
+(``ms_per_step`` is the time of one of them), the line.  ``--dump-outputs DIR`` adds the last timed step's
+outputs as ``DIR/<name>.npy`` (seeded inputs: the same arguments give the same inputs in every run);
+``--full`` is where measurements beyond the headline figure go.
 """
 from __future__ import annotations
 
@@ -83,7 +88,43 @@ def parse():
                     help=">0: NCCL_MIN_NCHANNELS = NCCL_MAX_NCHANNELS = this (RCCL honours both) before the "
                          "communicators are created; 0 leaves RCCL's own topology tuning")
     ap.add_argument("--json_out", default=None)
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step returned to DIR/<name>.npy: "
+                         "every loss term, the gradient norm, and a fixed seeded sample of the step's gradients and "
+                         "of the updated fp32 master weights (same arguments -> same inputs, so two builds compare "
+                         "output for output)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements and checks beyond the headline figure.  The plain run is set-up, "
+                         "warm-up, the timed steps and the result line only; anything that needs a run of its own "
+                         "belongs behind this flag (at present the benchmark has none)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+DUMP_SAMPLE = 1 << 21   # elements sampled from each parameter-sized arena: 8 MB of float32 per file
+
+
+def dump_outputs(path: str, res, store) -> None:
+    """``--dump-outputs``: the arrays a caller of the timed step receives, from its last run — the StepResult's
+    loss terms and gradient norm, and what the step left in the model: ``param.grad`` (zero_grad is lazy, so the
+    arena still holds the last step's gradients) and the updated fp32 master weights.  The two arenas are ~110 M
+    elements each, so a fixed seeded sample of ``DUMP_SAMPLE`` positions (the same for both) is written."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for k, v in res.losses.to_floats().items():
+        np.save(os.path.join(path, f"loss_{k}.npy"), np.array([v], dtype=np.float64))
+    if res.grad_norm is not None:
+        np.save(os.path.join(path, "grad_norm.npy"), res.grad_norm.detach().double().reshape(-1).cpu().numpy())
+    g = torch.Generator(device="cpu").manual_seed(20240521)
+    idx = torch.randint(0, store.total, (min(DUMP_SAMPLE, store.total),), generator=g).sort().values
+    idx = idx.to(store.master.device)
+    np.save(os.path.join(path, "grad_sample.npy"), store.grad.index_select(0, idx).float().cpu().numpy())
+    np.save(os.path.join(path, "weight_sample.npy"), store.master.index_select(0, idx).float().cpu().numpy())
 
 
 def selflaunch_cmd(argv, nproc: int, port: int):
@@ -170,6 +211,9 @@ def main():
     if world != args.gpus:   # never report an N-GPU label for a different job size
         raise SystemExit(f"[bench] error: --gpus {args.gpus} but the job has {world} rank(s)")
 
+    # every forward draws its dropout seed from torch's global generator: seeded, so that the same arguments give the
+    # same masks (with the seeded weights and batches: the same inputs) in every run
+    torch.manual_seed(1234 + rank)
     cfg = get_config(args.model)
     model = BertForQuestionAnswering(cfg, seed=1234, precision=args.precision).to(device).train()
     model.fp8_dgrad = bool(args.fp8_dgrad)
@@ -293,6 +337,8 @@ def main():
     ar_bytes = ((reducer.stats["bytes"] - bytes0) / args.steps) if reducer is not None else 0
     final_loss = res.losses.to_floats().get("loss", float("nan"))
     comm = reducer.pop_timings() if reducer is not None else {}
+    if args.dump_outputs and rank == 0:   # before the replica check's extra step overwrites the gradients
+        dump_outputs(args.dump_outputs, res, model.store)
     # data-parallel self-check, AFTER the clock: one more (untimed) step fingerprints its reduced gradient arena,
     # then every rank's fp32 master weights and that gradient are all-gathered and compared with rank 0's — a
     # reducer bug must fail the run, not be reported as a fast number

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import pytest
 import torch
 
 from conftest import ROOT, free_port
@@ -44,6 +45,69 @@ def test_bench_refuses_more_gpus_than_visible_on_cpu():
                        env={k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")})
     assert r.returncode == 2 and f"--gpus {n + 1} requested" in r.stdout, r.stdout[-2000:]
     assert '"metric"' not in r.stdout
+
+
+def test_steps_must_be_positive(monkeypatch):
+    b = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        b.parse()
+    assert e.value.code == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "0", "--full"])
+    a = b.parse()
+    assert a.steps == 3 and a.warmup == 0 and a.full is True and a.dump_outputs is None
+
+
+def test_dump_outputs_writes_the_steps_arrays(tmp_path):
+    """``--dump-outputs``: every loss term, the gradient norm and the same seeded sample of the gradient and
+    master arenas, as float32 / float64 ``.npy`` files; the sample positions do not change from call to call."""
+    import numpy as np
+    from types import SimpleNamespace
+    from ml_recipe_distributed_pytorch_amd.models.losses import LossRecord
+    b = _bench_module()
+    total = 10_007
+    store = SimpleNamespace(total=total, master=torch.arange(total, dtype=torch.float32),
+                            grad=-torch.arange(total, dtype=torch.float32))
+    res = SimpleNamespace(losses=LossRecord({"cls": torch.tensor(0.25), "loss": torch.tensor(1.5)}),
+                          grad_norm=torch.tensor(3.0))
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), res, store)
+    got = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == ["grad_norm.npy", "grad_sample.npy", "loss_cls.npy", "loss_loss.npy", "weight_sample.npy"]
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert got["loss_loss.npy"].tolist() == [1.5] and got["loss_cls.npy"].tolist() == [0.25]
+    assert got["grad_norm.npy"].tolist() == [3.0]
+    w, g = got["weight_sample.npy"], got["grad_sample.npy"]
+    assert w.shape == g.shape == (total,) and np.array_equal(g, -w)   # one set of positions for both arenas
+    assert w.min() >= 0 and w.max() < total and len(np.unique(w)) > total // 2
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
+    for f, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f)), f
+    assert 2 * 4 * b.DUMP_SAMPLE + 1024 <= 64 << 20   # the two sampled files of a full-size model
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_last_timed_step(cuda, tmp_path):
+    """One small run with ``--full --dump-outputs``: the result line keeps its fields, ``--steps`` is the number
+    of timed steps, and the dumped loss is the last timed step's (the result line's ``final_loss``)."""
+    import json
+    import numpy as np
+    out, dump = tmp_path / "bench.json", tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--batch", "8", "--seq", "128", "--full", "--dump-outputs", str(dump), "--json_out", str(out)],
+                       cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=240)
+    assert r.returncode == 0, r.stdout[-4000:]
+    rec = json.loads(out.read_text())
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in rec, rec
+    assert rec["steps"] == 2 and rec["warmup"] == 1 and rec["ms_per_step"] > 0 and rec["unit"] == "samples/s", rec
+    assert abs(rec["value"] - 8 / (rec["ms_per_step"] * 1e-3)) <= 0.01 * rec["value"], rec
+    got = {f: np.load(dump / f) for f in os.listdir(dump)}
+    assert {"loss_loss.npy", "grad_norm.npy", "grad_sample.npy", "weight_sample.npy"} <= set(got)
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in got.values())
+    assert abs(float(got["loss_loss.npy"][0]) - rec["final_loss"]) <= 1e-4
+    assert np.count_nonzero(got["grad_sample.npy"]) > got["grad_sample.npy"].size // 2
+    assert sum(v.nbytes for v in got.values()) <= 64 << 20
 
 
 def _bcast_worker(rank, world, port, out):
