@@ -662,8 +662,8 @@ void adamw(Tensor master, c10::optional<Tensor> compute, Tensor grad, Tensor m, 
   TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 2, "chunks must be [n,2] int64");
   c10::DeviceGuard g(master.device());
   hq_adamw(ptr<float>(master), optr<uint16_t>(compute), ptr<float>(grad), ptr<float>(m), ptr<float>(v),
-           reinterpret_cast<const HqOptChunk*>(chunks.data_ptr()), (int)chunks.size(0), groups_of(lr, wd), (float)beta1,
-           (float)beta2, (float)eps, (float)step_mult, optr<float>(clip_coef), cur_stream());
+           reinterpret_cast<const HqOptChunk*>(chunks.data_ptr()), (int)chunks.size(0), groups_of(lr, wd), HqBeta(beta1),
+           HqBeta(beta2), (float)eps, (float)step_mult, optr<float>(clip_coef), cur_stream());
 }
 
 void adamod(Tensor master, c10::optional<Tensor> compute, Tensor grad, Tensor m, Tensor v, Tensor n, Tensor chunks,
@@ -674,10 +674,12 @@ void adamod(Tensor master, c10::optional<Tensor> compute, Tensor grad, Tensor m,
   check_opt(clip_coef, F32, "clip");
   TORCH_CHECK(grad.numel() == master.numel() && m.numel() == master.numel() && v.numel() == master.numel() &&
                   n.numel() == master.numel(), "arena sizes");
+  if (compute.has_value() && compute->defined()) TORCH_CHECK(compute->numel() == master.numel(), "compute size");
+  TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 2, "chunks must be [n,2] int64");
   c10::DeviceGuard g(master.device());
   hq_adamod(ptr<float>(master), optr<uint16_t>(compute), ptr<float>(grad), ptr<float>(m), ptr<float>(v), ptr<float>(n),
-            reinterpret_cast<const HqOptChunk*>(chunks.data_ptr()), (int)chunks.size(0), groups_of(lr, wd), (float)beta1,
-            (float)beta2, (float)beta3, (float)eps, (float)bias_corr, optr<float>(clip_coef), cur_stream());
+            reinterpret_cast<const HqOptChunk*>(chunks.data_ptr()), (int)chunks.size(0), groups_of(lr, wd), HqBeta(beta1),
+            HqBeta(beta2), HqBeta(beta3), (float)eps, (float)bias_corr, optr<float>(clip_coef), cur_stream());
 }
 
 void cast_f32_bf16(Tensor src, Tensor dst, double scale) {
@@ -685,6 +687,13 @@ void cast_f32_bf16(Tensor src, Tensor dst, double scale) {
   TORCH_CHECK(src.numel() == dst.numel(), "size");
   c10::DeviceGuard g(src.device());
   hq_cast_f32_bf16(ptr<float>(src), ptr<uint16_t>(dst), src.numel(), (float)scale, cur_stream());
+}
+
+void cast_bf16_f32(Tensor src, Tensor dst, double scale) {
+  check(src, BF16, "src"); check(dst, F32, "dst");
+  TORCH_CHECK(src.numel() == dst.numel(), "size");
+  c10::DeviceGuard g(src.device());
+  hq_cast_bf16_f32(ptr<uint16_t>(src), ptr<float>(dst), src.numel(), (float)scale, cur_stream());
 }
 
 // ------------------------------------------------------------------------ fused QA heads + losses
@@ -1099,6 +1108,7 @@ PYBIND11_MODULE(_hq_kernels, m) {
   m.def("adamw", &adamw);
   m.def("adamod", &adamod);
   m.def("cast_f32_bf16", &cast_f32_bf16);
+  m.def("cast_bf16_f32", &cast_bf16_f32);
   m.def("rccl_unique_id", []() { return py::bytes(hq_rccl_unique_id()); });
   py::class_<HqReducer>(m, "Reducer")
       .def(py::init([](int rank, int world, py::bytes uid, int device) {

@@ -132,11 +132,17 @@ void hq_fingerprint(const float* x, int64_t n, int nparts, uint64_t* out, hipStr
 constexpr int64_t kNormChunk = 1 << 18;
 void hq_sq_norm_chunks(const float* g, const int64_t* chunks, int c0, int c1, float* partials, hipStream_t s);
 void hq_clip_coef(const float* partials, int nparts, float max_norm, float* norm_out, float* coef_out, hipStream_t s);
+// An EMA coefficient with its complement, both rounded once from the double: (float)(1.0 - beta) is not
+// 1.f - (float)beta (0.001 against 0.00100004673 for beta = 0.999), so the kernels never subtract in fp32.
+struct HqBeta {
+  float beta, one_minus;
+  explicit HqBeta(double b) : beta((float)b), one_minus((float)(1.0 - b)) {}
+};
 void hq_adamw(float* master, uint16_t* compute, const float* grad, float* m, float* v, const HqOptChunk* chunks,
-              int nchunks, HqOptGroups groups, float beta1, float beta2, float eps, float step_size_mult,
+              int nchunks, HqOptGroups groups, HqBeta beta1, HqBeta beta2, float eps, float step_size_mult,
               const float* clip_coef, hipStream_t s);
 void hq_adamod(float* master, uint16_t* compute, const float* grad, float* m, float* v, float* n, const HqOptChunk* chunks,
-               int nchunks, HqOptGroups groups, float beta1, float beta2, float beta3, float eps, float bias_corr,
+               int nchunks, HqOptGroups groups, HqBeta beta1, HqBeta beta2, HqBeta beta3, float eps, float bias_corr,
                const float* clip_coef, hipStream_t s);
 void hq_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, float scale, hipStream_t s);
 void hq_cast_bf16_f32(const uint16_t* src, float* dst, int64_t n, float scale, hipStream_t s);

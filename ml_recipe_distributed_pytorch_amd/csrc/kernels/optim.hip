@@ -75,13 +75,15 @@ __global__ __launch_bounds__(256) void clip_coef_kernel(const float* __restrict_
   }
 }
 
+// om1 / om2 (/ om3): 1 − β rounded ONCE from the double on the host.  1.f − β in fp32 from the fp32-rounded β is
+// 0.00100004673 for β2 = 0.999, a 4.7e-5 relative error in every (1−β2)·g² increment (docs/PARITY.md).
 struct AdamWArgs {
-  float beta1, beta2, eps, step_mult;
+  float beta1, beta2, om1, om2, eps, step_mult;
 };
 
 __device__ __forceinline__ void adamw_elem(float& p, float& m, float& v, float g, float lr, float wd, const AdamWArgs& a) {
-  m = a.beta1 * m + (1.f - a.beta1) * g;
-  v = a.beta2 * v + (1.f - a.beta2) * g * g;
+  m = a.beta1 * m + a.om1 * g;
+  v = a.beta2 * v + a.om2 * g * g;
   const float denom = sqrtf(v) + a.eps;
   p = p - (lr * a.step_mult) * (m / denom);
   if (wd > 0.f) p = p - (lr * wd) * p;
@@ -162,7 +164,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ master, 
 }
 
 struct AdaModArgs {
-  float beta1, beta2, beta3, eps, base;  // base = bias-corrected step-size factor (times lr per group)
+  float beta1, beta2, beta3, om1, om2, om3, eps, base;  // base = bias-corrected step-size factor (times lr per group)
 };
 
 __global__ __launch_bounds__(256) void adamod_kernel(float* __restrict__ master, uint16_t* __restrict__ compute,
@@ -176,13 +178,13 @@ __global__ __launch_bounds__(256) void adamod_kernel(float* __restrict__ master,
   for (int i = threadIdx.x; i < c.numel; i += 256) {
     const int64_t o = c.start + i;
     const float g = grad[o] * cc;
-    float m = a.beta1 * exp_avg[o] + (1.f - a.beta1) * g;
-    float v = a.beta2 * exp_avg_sq[o] + (1.f - a.beta2) * g * g;
+    float m = a.beta1 * exp_avg[o] + a.om1 * g;
+    float v = a.beta2 * exp_avg_sq[o] + a.om2 * g * g;
     const float denom = sqrtf(v) + a.eps;
     float p = master[o];
     if (wd != 0.f) p = p - (wd * lr) * p;
     float ss = (lr * a.base) / denom;
-    const float n = a.beta3 * exp_avg_lr[o] + (1.f - a.beta3) * ss;
+    const float n = a.beta3 * exp_avg_lr[o] + a.om3 * ss;
     ss = fminf(ss, n) * m;
     p = p - ss;
     exp_avg[o] = m;
@@ -262,16 +264,16 @@ void hq_clip_coef(const float* partials, int nparts, float max_norm, float* norm
 }
 
 void hq_adamw(float* master, uint16_t* compute, const float* grad, float* m, float* v, const HqOptChunk* chunks, int nchunks,
-              HqOptGroups groups, float beta1, float beta2, float eps, float step_size_mult, const float* clip_coef,
+              HqOptGroups groups, HqBeta beta1, HqBeta beta2, float eps, float step_size_mult, const float* clip_coef,
               hipStream_t s) {
-  AdamWArgs a{beta1, beta2, eps, step_size_mult};
+  AdamWArgs a{beta1.beta, beta2.beta, beta1.one_minus, beta2.one_minus, eps, step_size_mult};
   hipLaunchKernelGGL(adamw_kernel, dim3(nchunks), dim3(256), 0, s, master, compute, grad, m, v, chunks, groups, a, clip_coef);
 }
 
 void hq_adamod(float* master, uint16_t* compute, const float* grad, float* m, float* v, float* n, const HqOptChunk* chunks,
-               int nchunks, HqOptGroups groups, float beta1, float beta2, float beta3, float eps, float bias_corr,
+               int nchunks, HqOptGroups groups, HqBeta beta1, HqBeta beta2, HqBeta beta3, float eps, float bias_corr,
                const float* clip_coef, hipStream_t s) {
-  AdaModArgs a{beta1, beta2, beta3, eps, bias_corr};
+  AdaModArgs a{beta1.beta, beta2.beta, beta3.beta, beta1.one_minus, beta2.one_minus, beta3.one_minus, eps, bias_corr};
   hipLaunchKernelGGL(adamod_kernel, dim3(nchunks), dim3(256), 0, s, master, compute, grad, m, v, n, chunks, groups, a,
                      clip_coef);
 }

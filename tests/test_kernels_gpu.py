@@ -344,6 +344,7 @@ def test_adamw_and_norm(cuda):
                    eps=1e-6, clip_coef=coef.cpu(), correct_bias=False, step=1)
     _close(md, master, 1e-6, 1e-5, "master")
     _close(mmd, m, 1e-7, 1e-5, "exp_avg")
+    _close(vvd, v, 1e-9, 1e-5, "exp_avg_sq")
     _close(comp, master, 1e-2, 1e-2, "bf16 copy")
 
 
