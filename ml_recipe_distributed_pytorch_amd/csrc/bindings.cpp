@@ -61,7 +61,11 @@ std::vector<Tensor> embed_fwd(Tensor ids, Tensor pids, Tensor tids, Tensor ww, T
 
 void embed_bwd(Tensor dy, Tensor ids, Tensor pids, Tensor tids, Tensor ww, Tensor wp, Tensor wt, Tensor gamma, Tensor mean,
                Tensor rstd, double p, int64_t seed, int64_t opid, Tensor g_word, Tensor g_pos, Tensor g_type, Tensor g_gamma,
-               Tensor g_beta, bool accumulate, int64_t pad_word, int64_t pad_pos, int64_t seq_len) {
+               Tensor g_beta, bool accumulate, int64_t pad_word, int64_t pad_pos, int64_t seq_len, bool deterministic,
+               bool det_positions) {
+  // deterministic: with more than 2 types the type gradients come from sorted runs instead of atomics;
+  // det_positions: so do ALL position gradients (for position ids that are not each row's column index — the
+  // caller knows, the host never looks at the ids).  Both off: the default paths, unchanged.
   check(dy, BF16, "dy"); check(ids, I64, "ids"); check(pids, I64, "pos_ids"); check(tids, I64, "type_ids");
   check(ww, BF16, "w_word"); check(wp, BF16, "w_pos"); check(wt, BF16, "w_type"); check(gamma, F32, "gamma");
   check(mean, F32, "mean"); check(rstd, F32, "rstd");
@@ -83,11 +87,15 @@ void embed_bwd(Tensor dy, Tensor ids, Tensor pids, Tensor tids, Tensor ww, Tenso
   const int V = (int)ww.size(0);
   const HqEmbScratchSizes zs = hq_embed_bwd_scratch((int)T, V, (int)seq_len, (int)wp.size(0));
   auto pairs = at::empty({4, T}, ids.options().dtype(at::kInt));
-  auto sort_tmp = at::empty({(int64_t)std::max<size_t>(zs.sort_bytes, 1)}, ids.options().dtype(at::kByte));
+  // the position / type sorts of the deterministic modes reuse the word sort's scratch: room for the largest
+  size_t sort_bytes = zs.sort_bytes;
+  if (det_positions) sort_bytes = std::max(sort_bytes, hq_sort_ids_bytes((int)T, (int)wp.size(0)));
+  if (deterministic && n_types > 2) sort_bytes = std::max(sort_bytes, hq_sort_ids_bytes((int)T, n_types));
+  auto sort_tmp = at::empty({(int64_t)std::max<size_t>(sort_bytes, 1)}, ids.options().dtype(at::kByte));
   auto carry = at::empty({(int64_t)zs.chunks * 2, H}, gamma.options());
-  auto ppart = at::empty({std::max<int64_t>(zs.pos_rows, 1), H}, gamma.options());
+  auto ppart = at::empty({std::max<int64_t>(det_positions ? 0 : zs.pos_rows, 1), H}, gamma.options());
   int32_t* pr = pairs.data_ptr<int32_t>();
-  const HqEmbScratch sc{pr, pr + T, pr + 2 * T, pr + 3 * T, sort_tmp.data_ptr(), zs.sort_bytes, ptr<float>(carry),
+  const HqEmbScratch sc{pr, pr + T, pr + 2 * T, pr + 3 * T, sort_tmp.data_ptr(), sort_bytes, ptr<float>(carry),
                         ptr<float>(ppart)};
   float* t0 = ptr<float>(g_type);
   HqOuts o = outs4(ptr<float>(g_gamma), ptr<float>(g_beta), n_types <= 2 ? t0 : nullptr,
@@ -95,7 +103,8 @@ void embed_bwd(Tensor dy, Tensor ids, Tensor pids, Tensor tids, Tensor ww, Tenso
   hq_embed_bwd(ptr<uint16_t>(dy), ptr<int64_t>(ids), ptr<int64_t>(pids), ptr<int64_t>(tids), ptr<uint16_t>(ww),
                ptr<uint16_t>(wp), ptr<uint16_t>(wt), ptr<float>(gamma), ptr<float>(mean), ptr<float>(rstd),
                ptr<float>(g_word), ptr<float>(g_pos), t0, ptr<float>(part), o, (int)T, (int)H, n_types, (int)pad_word,
-               (int)pad_pos, (float)p, u32(seed), u32(opid), accumulate, V, (int)wp.size(0), (int)seq_len, sc, s);
+               (int)pad_pos, (float)p, u32(seed), u32(opid), accumulate, V, (int)wp.size(0), (int)seq_len, sc, s,
+               det_positions, deterministic);
 }
 
 // ------------------------------------------------------------------ residual + dropout + LayerNorm
@@ -840,7 +849,7 @@ std::vector<Tensor> f32_embed_fwd(Tensor ids, Tensor pids, Tensor tids, Tensor w
 
 void f32_embed_bwd(Tensor dy, Tensor ids, Tensor pids, Tensor tids, Tensor ww, Tensor wp, Tensor wt, Tensor gamma, Tensor mean,
                    Tensor rstd, double p, int64_t seed, int64_t opid, Tensor g_word, Tensor g_pos, Tensor g_type,
-                   Tensor g_gamma, Tensor g_beta, bool accumulate, int64_t pad_word, int64_t pad_pos) {
+                   Tensor g_gamma, Tensor g_beta, bool accumulate, int64_t pad_word, int64_t pad_pos, bool deterministic) {
   check(ids, I64, "ids"); check(pids, I64, "pos_ids"); check(tids, I64, "type_ids");
   for (auto* t : {&dy, &ww, &wp, &wt, &gamma, &mean, &rstd, &g_word, &g_pos, &g_type, &g_gamma, &g_beta}) f32_rows(*t, "f32 operand");
   const int64_t T = ids.numel(), H = ww.size(1);
@@ -855,13 +864,27 @@ void f32_embed_bwd(Tensor dy, Tensor ids, Tensor pids, Tensor tids, Tensor ww, T
     if (n_types > 2) hq_zero_f32(ptr<float>(g_type), (size_t)g_type.numel(), s);   // else folded from partials
   }
   auto part = at::empty({hq_f32_part_rows((int)T), 4 * H}, dy.options());
+  // deterministic: per-call scratch of the sorted-run path (sort pairs, digit histograms of the widest key, carry
+  // rows), shared by the word, position and type passes
+  Tensor pairs, sort_tmp, carry;
+  HqEmbScratch sc{};
+  if (deterministic) {
+    const int V = (int)ww.size(0), P = (int)wp.size(0);
+    size_t sort_bytes = std::max(hq_sort_ids_bytes((int)T, V), hq_sort_ids_bytes((int)T, P));
+    if (n_types > 2) sort_bytes = std::max(sort_bytes, hq_sort_ids_bytes((int)T, n_types));
+    pairs = at::empty({4, T}, ids.options().dtype(at::kInt));
+    sort_tmp = at::empty({(int64_t)std::max<size_t>(sort_bytes, 1)}, ids.options().dtype(at::kByte));
+    carry = at::empty({(int64_t)std::max(hq_f32_embed_run_chunks((int)T), 1) * 2, H}, dy.options());
+    int32_t* pr = pairs.data_ptr<int32_t>();
+    sc = HqEmbScratch{pr, pr + T, pr + 2 * T, pr + 3 * T, sort_tmp.data_ptr(), sort_bytes, ptr<float>(carry), nullptr};
+  }
   float* t0 = ptr<float>(g_type);
   hq_f32_embed_bwd(ptr<float>(dy), ptr<int64_t>(ids), ptr<int64_t>(pids), ptr<int64_t>(tids), ptr<float>(ww), ptr<float>(wp),
                    ptr<float>(wt), ptr<float>(gamma), ptr<float>(mean), ptr<float>(rstd), ptr<float>(g_word),
                    ptr<float>(g_pos), t0, ptr<float>(part),
                    outs4(ptr<float>(g_gamma), ptr<float>(g_beta), n_types <= 2 ? t0 : nullptr, n_types == 2 ? t0 + H : nullptr),
                    (int)T, (int)H, (int)pad_word, (int)pad_pos, (float)p, u32(seed), u32(opid), accumulate,
-                   (int)ww.size(0), (int)wp.size(0), (int)wt.size(0), s);
+                   (int)ww.size(0), (int)wp.size(0), (int)wt.size(0), s, deterministic ? &sc : nullptr);
 }
 
 std::vector<Tensor> f32_ln_fwd(Tensor a, Tensor resid, Tensor gamma, Tensor beta, double eps, double p, int64_t seed,
@@ -957,7 +980,9 @@ PYBIND11_MODULE(_hq_kernels, m) {
   m.def("embed_bwd", &embed_bwd, py::arg("dy"), py::arg("ids"), py::arg("pids"), py::arg("tids"), py::arg("ww"),
         py::arg("wp"), py::arg("wt"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"), py::arg("p"), py::arg("seed"),
         py::arg("opid"), py::arg("g_word"), py::arg("g_pos"), py::arg("g_type"), py::arg("g_gamma"), py::arg("g_beta"),
-        py::arg("accumulate"), py::arg("pad_word"), py::arg("pad_pos"), py::arg("seq_len") = 0);
+        py::arg("accumulate"), py::arg("pad_word"), py::arg("pad_pos"), py::arg("seq_len") = 0,
+        py::arg("deterministic") = false, py::arg("det_positions") = false);
+  m.def("embed_run_chunk", []() { return kHqEmbRunChunk; });   // the unit of the sorted-run summation order
   m.def("ln_fwd", &ln_fwd, py::arg("a"), py::arg("resid"), py::arg("gamma"), py::arg("beta"), py::arg("eps"), py::arg("p"),
         py::arg("seed"), py::arg("opid"), py::arg("q8") = py::none(), py::arg("phase") = 0, py::arg("store_z") = true);
   m.def("ln_bwd", &ln_bwd, py::arg("dy"), py::arg("dy2"), py::arg("z"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"),
@@ -989,7 +1014,10 @@ PYBIND11_MODULE(_hq_kernels, m) {
   m.def("transpose_tiles8", &transpose_tiles8);
   m.def("colsum_into", &colsum_into);
   m.def("f32_embed_fwd", &f32_embed_fwd);
-  m.def("f32_embed_bwd", &f32_embed_bwd);
+  m.def("f32_embed_bwd", &f32_embed_bwd, py::arg("dy"), py::arg("ids"), py::arg("pids"), py::arg("tids"), py::arg("ww"),
+        py::arg("wp"), py::arg("wt"), py::arg("gamma"), py::arg("mean"), py::arg("rstd"), py::arg("p"), py::arg("seed"),
+        py::arg("opid"), py::arg("g_word"), py::arg("g_pos"), py::arg("g_type"), py::arg("g_gamma"), py::arg("g_beta"),
+        py::arg("accumulate"), py::arg("pad_word"), py::arg("pad_pos"), py::arg("deterministic") = false);
   m.def("f32_ln_fwd", &f32_ln_fwd);
   m.def("f32_ln_bwd", &f32_ln_bwd, py::arg("dy"), py::arg("dy2"), py::arg("z"), py::arg("gamma"), py::arg("mean"),
         py::arg("rstd"), py::arg("p"), py::arg("seed"), py::arg("opid"), py::arg("g_gamma"), py::arg("g_beta"),

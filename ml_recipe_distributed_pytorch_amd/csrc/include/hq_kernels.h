@@ -58,11 +58,17 @@ HqEmbScratchSizes hq_embed_bwd_scratch(int T, int V, int L, int P);
 size_t hq_sort_ids_bytes(int T, int V);
 void hq_sort_ids(const int64_t* ids, int T, int V, int32_t* keys, int32_t* rows, int32_t* skeys, int32_t* srows,
                  void* hist, size_t hist_bytes, hipStream_t s);
+// sorted rows per wave of the sorted-run kernels (norm.hip embed_word_kernel, f32_ops.hip f32_embed_run_kernel): the
+// unit of their documented summation order
+constexpr int kHqEmbRunChunk = 16;
+// det_pos: every position gradient from a sort of pids + the sorted-run kernels (no position partials, no position
+// atomics); det_type: with n_types > 2 the type gradients likewise from a sort of tids.  Either needs sort_tmp to
+// cover hq_sort_ids_bytes(T, P) / (T, n_types) as well.
 void hq_embed_bwd(const uint16_t* dy, const int64_t* ids, const int64_t* pids, const int64_t* tids, const uint16_t* ww,
                   const uint16_t* wp, const uint16_t* wt, const float* gamma, const float* mean, const float* rstd,
                   float* g_word, float* g_pos, float* g_type, float* part, HqOuts outs, int T, int H, int n_types,
                   int pad_word, int pad_pos, float p, uint32_t seed, uint32_t opid, bool accumulate, int V, int P,
-                  int L, const HqEmbScratch& sc, hipStream_t s);
+                  int L, const HqEmbScratch& sc, hipStream_t s, bool det_pos = false, bool det_type = false);
 // partial-sum rows embed_bwd needs for T tokens laid out as [T / L][L] (L <= 0: one sequence)
 int hq_embed_bwd_partials(int T, int L);
 void hq_gelu_fwd(const uint16_t* pre, uint16_t* out, size_t n, hipStream_t s);
@@ -74,11 +80,15 @@ int hq_f32_part_rows(int T);      // rows to allocate for their `part` scratch (
 void hq_f32_embed_fwd(const int64_t* ids, const int64_t* pids, const int64_t* tids, const float* ww, const float* wp,
                       const float* wt, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int T, int H,
                       float eps, float p, uint32_t seed, uint32_t opid, int V, int P, int NTY, hipStream_t s);
+// det != null: no float atomics — every table row is summed over its key-sorted run in a fixed order.  Scratch:
+// keys / rows / skeys / srows [T], sort_tmp of the largest hq_sort_ids_bytes(T, V | P | NTY), carry
+// [hq_f32_embed_run_chunks(T)][2][H]; ppart unused.
 void hq_f32_embed_bwd(const float* dy, const int64_t* ids, const int64_t* pids, const int64_t* tids, const float* ww,
                       const float* wp, const float* wt, const float* gamma, const float* mean, const float* rstd,
                       float* g_word, float* g_pos, float* g_type, float* part, HqOuts outs, int T, int H, int pad_word,
                       int pad_pos, float p, uint32_t seed, uint32_t opid, bool accumulate, int V, int P, int NTY,
-                      hipStream_t s);
+                      hipStream_t s, const HqEmbScratch* det = nullptr);
+int hq_f32_embed_run_chunks(int T);
 void hq_f32_ln_fwd(const float* a, const float* resid, const float* gamma, const float* beta, float* y, float* z, float* mean,
                    float* rstd, int T, int H, float eps, float p, uint32_t seed, uint32_t opid, hipStream_t s);
 void hq_f32_ln_bwd(const float* dy, const float* dy2, const float* z, const float* gamma, const float* beta, const float* mean,

@@ -5,7 +5,8 @@
 // row runs here instead of as ATen ops — fp32 in, fp32 out, fp32 statistics, dropout masks from the same counter
 // hash as every other kernel (hq_keep, bit-identical to ops/rng.py), so the GPU fp32 model reproduces the CPU
 // oracle (ops/reference.py) op for op:
-//   f32_embed_fwd / _bwd   : 3 gathers + LayerNorm + dropout; backward with f32 atomics into the tables
+//   f32_embed_fwd / _bwd   : 3 gathers + LayerNorm + dropout; backward into the tables with f32 atomics (default) or,
+//                            deterministic, by key-sorted runs summed in a fixed order (f32_embed_run_kernel)
 //   f32_ln_fwd / _bwd      : z = dropout(a) + resid, y = LN(z); backward dz, da and γ / β / bias column partials
 //   f32_gelu_fwd / _bwd    : erf GELU; backward with the producing Linear's bias-gradient column partials
 //   f32_colsum             : column partials of a [T, N] matrix (the Linear bias gradients), then a fixed-order fold
@@ -72,8 +73,9 @@ __global__ __launch_bounds__(256) void f32_embed_fwd_kernel(const int64_t* __res
   if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
 }
 
-// rows [blockIdx.x·kRowsPerBlock, +kRowsPerBlock), one wave per row at a time; γ / β partials per block
-template <int NC>
+// rows [blockIdx.x·kRowsPerBlock, +kRowsPerBlock), one wave per row at a time; γ / β partials per block.
+// DET: no table scatter here — the word / position / type (NTY > 2) rows come from f32_embed_run_kernel.
+template <int NC, bool DET>
 __global__ __launch_bounds__(256) void f32_embed_bwd_kernel(const float* __restrict__ dy, const int64_t* __restrict__ ids,
                                                             const int64_t* __restrict__ pids, const int64_t* __restrict__ tids,
                                                             const float* __restrict__ ww, const float* __restrict__ wp,
@@ -124,9 +126,11 @@ __global__ __launch_bounds__(256) void f32_embed_bwd_kernel(const float* __restr
       const int col = c * 64 + lane;
       if (col < H) {
         const float dx = rs * (g[c] * gam[c] - s1 - xh[c] * s2);
-        if (id != pad_word) atomicAdd(g_word + id * H + col, dx);
-        if (pid != pad_pos) atomicAdd(g_pos + pid * H + col, dx);
-        if (!tpart) atomicAdd(g_type + tid * H + col, dx);
+        if (!DET) {
+          if (id != pad_word) atomicAdd(g_word + id * H + col, dx);
+          if (pid != pad_pos) atomicAdd(g_pos + pid * H + col, dx);
+          if (!tpart) atomicAdd(g_type + tid * H + col, dx);
+        }
         at0[c] += tid == 0 ? dx : 0.f;
         at1[c] += tid == 1 ? dx : 0.f;
       }
@@ -143,6 +147,159 @@ __global__ __launch_bounds__(256) void f32_embed_bwd_kernel(const float* __restr
   for (int i = threadIdx.x; i < 4 * H; i += 256) {
     const int w = i / H, col = i - w * H;
     part[(size_t)blockIdx.x * 4 * H + i] = (red[0][w][col] + red[1][w][col]) + (red[2][w][col] + red[3][w][col]);
+  }
+}
+
+// ---- deterministic table gradients: sorted runs instead of atomics (hq_f32_embed_bwd with deterministic = true)
+// One pair of kernels serves the word, position and type tables; KEY picks which id of a token is the key
+// (0: ids, 1: pids, 2: tids).  The tokens are sorted by key with the stable hq_sort_ids, so the tokens of one key
+// (its "run") are contiguous in the sorted list and stay in token order.  The summation order of a table row is:
+//   * the sorted list is cut into chunks of kRunCH consecutive sorted positions, chunk c = [c·kRunCH, (c+1)·kRunCH),
+//     one wave per chunk; the rows of ONE key inside ONE chunk form a piece;
+//   * a piece is summed from zero in token order: piece = ((0 + dx[t0]) + dx[t1]) + …, every dx recomputed by the
+//     wave exactly as f32_embed_bwd_kernel computes it;
+//   * a run that lies inside one chunk is one piece; a run that crosses chunk boundaries has one piece per chunk
+//     it touches, and the pieces are added in chunk order onto the first: total = ((piece_c + piece_c+1) + …);
+//   * accumulate adds the existing table row last: row = total + row; fresh stores row = total;
+//   * the skipped key (the padding id / padding position) gets no gradient, a key that never occurs keeps its row.
+// Pieces of crossing runs travel through the carry buffer [chunks][2][H]: slot 0 of chunk c holds the chunk's first
+// piece when its run began in an earlier chunk, slot 1 the chunk's last piece when its run began in this chunk and
+// continues into the next; f32_embed_carry_kernel, run by the chunk that holds slot 1, completes the row.
+constexpr int kRunCH = kHqEmbRunChunk;   // sorted rows per wave (<= 64: one row's metadata per lane)
+
+template <int NC, int KEY>
+__global__ __launch_bounds__(256) void f32_embed_run_kernel(
+    const int32_t* __restrict__ skeys, const int32_t* __restrict__ srows, const float* __restrict__ dy,
+    const int64_t* __restrict__ ids, const int64_t* __restrict__ pids, const int64_t* __restrict__ tids,
+    const float* __restrict__ ww, const float* __restrict__ wp, const float* __restrict__ wt,
+    const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ rstd,
+    float* __restrict__ g_dst, float* __restrict__ carry, int T, int H, int pad_key, int accumulate, int NK, int V,
+    int P, int NTY, HqDropKey kd, uint32_t thr, float ks) {
+  static_assert(kRunCH <= 64, "one row's metadata per lane");
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c = blockIdx.x * kW + wave;
+  const int j0 = c * kRunCH;
+  if (j0 >= T) return;
+  const int j1 = min(T, j0 + kRunCH);
+  const uint32_t key = kd.get();
+  float gam[NC], acc[NC];
+#pragma unroll
+  for (int q = 0; q < NC; ++q) {
+    acc[q] = 0.f;
+    gam[q] = q * 64 + lane < H ? gamma[q * 64 + lane] : 0.f;
+  }
+  const int first = __builtin_amdgcn_readfirstlane(skeys[j0]);
+  const bool head_cont = c > 0 && __builtin_amdgcn_readfirstlane(skeys[j0 - 1]) == first;
+  const int after = j1 < T ? __builtin_amdgcn_readfirstlane(skeys[j1]) : -1;
+  auto flush = [&](int k, int kind) {   // kind 0: carry slot 0, 1: carry slot 1, 2: the gradient row
+    if (k != pad_key) {
+      HQ_DASSERT(kind == 2 ? (k >= 0 && k < NK) : (kind >= 0 && kind < 2 && c >= 0 && c * kRunCH < T));
+      float* dst = kind == 2 ? g_dst + (size_t)k * H : carry + ((size_t)c * 2 + kind) * H;
+#pragma unroll
+      for (int q = 0; q < NC; ++q) {
+        const int col = q * 64 + lane;
+        if (col < H) dst[col] = (kind == 2 && accumulate) ? acc[q] + dst[col] : acc[q];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < NC; ++q) acc[q] = 0.f;
+  };
+  // the chunk's sorted rows and their metadata, one per lane
+  const bool ok = lane < j1 - j0;
+  const int myrow = ok ? srows[j0 + lane] : 0;
+  HQ_DASSERT(myrow >= 0 && myrow < T);
+  const int mid = ok ? (int)ids[myrow] : 0, mpid = ok ? (int)pids[myrow] : 0, mtid = ok ? (int)tids[myrow] : 0;
+  const float mmu = ok ? mean[myrow] : 0.f, mrs = ok ? rstd[myrow] : 0.f;
+  int seg = first;
+  bool seg_first = true;
+#pragma unroll 1
+  for (int j = j0; j < j1; ++j) {
+    const int r = j - j0;
+    const size_t row = (size_t)__builtin_amdgcn_readlane(myrow, r);
+    const int id = __builtin_amdgcn_readlane(mid, r), pid = __builtin_amdgcn_readlane(mpid, r),
+              tid = __builtin_amdgcn_readlane(mtid, r);
+    const float mu = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mmu), r));
+    const float rs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mrs), r));
+    HQ_DASSERT(id >= 0 && id < V && pid >= 0 && pid < P && tid >= 0 && tid < NTY && row < (size_t)T);
+    const int k = KEY == 0 ? id : (KEY == 1 ? pid : tid);
+    HQ_DASSERT(k == skeys[j] && k >= 0 && k < NK);
+    if (k != seg) {
+      flush(seg, seg_first && head_cont ? 0 : 2);
+      seg = k;
+      seg_first = false;
+    }
+    float xh[NC], g[NC], s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int q = 0; q < NC; ++q) {
+      const int col = q * 64 + lane;
+      if (col < H) {
+        const float x = ww[(size_t)id * H + col] + wp[(size_t)pid * H + col] + wt[(size_t)tid * H + col];
+        xh[q] = (x - mu) * rs;
+        g[q] = dy[row * H + col] * keep_mul((uint32_t)(row * H + col), key, thr, ks);
+      } else {
+        xh[q] = g[q] = 0.f;
+      }
+      const float d = g[q] * gam[q];
+      s1 += d;
+      s2 += d * xh[q];
+    }
+    s1 = hq_wave_sum(s1) / H;
+    s2 = hq_wave_sum(s2) / H;
+#pragma unroll
+    for (int q = 0; q < NC; ++q) {
+      // dx is rounded on its own and then added: a multiply fused into the running sum would make the piece
+      // something other than the sum of its rows' dx
+#pragma clang fp contract(off)
+      const float dx = rs * (g[q] * gam[q] - s1 - xh[q] * s2);
+      if (q * 64 + lane < H) acc[q] += dx;
+    }
+  }
+  const bool from_prev = seg_first && head_cont;
+  flush(seg, from_prev ? 0 : (after == seg ? 1 : 2));
+}
+
+// Runs that cross chunk boundaries: the chunk holding a run's first piece (carry slot 1) adds the following chunks'
+// slot-0 pieces in chunk order, then the existing row (accumulate), and stores the gradient row.
+template <int NC>
+__global__ __launch_bounds__(256) void f32_embed_carry_kernel(const int32_t* __restrict__ skeys,
+                                                              const float* __restrict__ carry, float* __restrict__ g_dst,
+                                                              int T, int H, int pad_key, int accumulate, int NK) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int c = blockIdx.x * kW + wave;
+  const int j0 = c * kRunCH;
+  if (j0 >= T) return;
+  const int j1 = min(T, j0 + kRunCH);
+  const int last = __builtin_amdgcn_readfirstlane(skeys[j1 - 1]);
+  if (j1 >= T || skeys[j1] != last || last == pad_key) return;        // the last run ends here (or gets nothing)
+  if (skeys[j0] == last && c > 0 && skeys[j0 - 1] == last) return;    // ... or began before: that chunk completes it
+  // end of the run: the first sorted position past j1 whose key differs, by a 64-ary search over the sorted keys
+  int lo = j1, hi = T;   // skeys[lo] == last; the end lies in (lo, hi]
+  while (hi - lo > 1) {
+    const int step = (hi - lo + 63) / 64;
+    const int q = lo + lane * step;
+    const bool in = q < hi && skeys[q] == last;
+    const uint64_t m = __ballot(in);   // a non-empty prefix of the lanes (sorted keys, skeys[lo] == last)
+    const int k = 63 - __builtin_clzll(m);
+    lo = lo + k * step;
+    hi = min(hi, lo + step);
+  }
+  const int ce = (hi - 1) / kRunCH;   // the last chunk holding rows of the run: pieces of chunks c+1 … ce
+  HQ_DASSERT(last >= 0 && last < NK && hi <= T && ce * kRunCH < T && ce > c);
+  float acc[NC];
+#pragma unroll
+  for (int q = 0; q < NC; ++q) acc[q] = q * 64 + lane < H ? carry[((size_t)c * 2 + 1) * H + q * 64 + lane] : 0.f;
+  for (int cc = c + 1; cc <= ce; ++cc) {
+    float v[NC];
+#pragma unroll
+    for (int q = 0; q < NC; ++q) v[q] = q * 64 + lane < H ? carry[(size_t)cc * 2 * H + q * 64 + lane] : 0.f;
+#pragma unroll
+    for (int q = 0; q < NC; ++q) acc[q] += v[q];
+  }
+  float* dst = g_dst + (size_t)last * H;
+#pragma unroll
+  for (int q = 0; q < NC; ++q) {
+    const int col = q * 64 + lane;
+    if (col < H) dst[col] = accumulate ? acc[q] + dst[col] : acc[q];
   }
 }
 
@@ -554,6 +711,7 @@ void fold(float* part, int nb, int width, int nout, HqOuts outs, bool accumulate
 
 int hq_f32_row_partials(int T) { return (T + kRowsPerBlock - 1) / kRowsPerBlock; }
 int hq_f32_part_rows(int T) { return hq_f32_row_partials(T) + kFoldS; }
+int hq_f32_embed_run_chunks(int T) { return (T + kRunCH - 1) / kRunCH; }
 
 void hq_f32_embed_fwd(const int64_t* ids, const int64_t* pids, const int64_t* tids, const float* ww, const float* wp,
                       const float* wt, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int T, int H,
@@ -570,14 +728,32 @@ void hq_f32_embed_bwd(const float* dy, const int64_t* ids, const int64_t* pids, 
                       const float* wp, const float* wt, const float* gamma, const float* mean, const float* rstd,
                       float* g_word, float* g_pos, float* g_type, float* part, HqOuts outs, int T, int H, int pad_word,
                       int pad_pos, float p, uint32_t seed, uint32_t opid, bool accumulate, int V, int P, int NTY,
-                      hipStream_t s) {
+                      hipStream_t s, const HqEmbScratch* det) {
   const uint32_t thr = p > 0.f ? hq_threshold(p) : 0u;
   const HqDropKey kd = hq_drop_key(seed, opid);
+  const float kss = hq_keep_scale(thr);
   const int nb = hq_f32_row_partials(T);
   dispatch_nc(H, [&](auto nc) {
-    hipLaunchKernelGGL(f32_embed_bwd_kernel<decltype(nc)::value>, dim3(nb), dim3(256), 0, s, dy, ids, pids, tids, ww, wp, wt,
-                       gamma, mean, rstd, g_word, g_pos, g_type, part, T, H, pad_word, pad_pos, V, P, NTY, kd, thr,
-                       hq_keep_scale(thr));
+    constexpr int C = decltype(nc)::value;
+    auto go = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(nb), dim3(256), 0, s, dy, ids, pids, tids, ww, wp, wt, gamma, mean, rstd, g_word, g_pos,
+                         g_type, part, T, H, pad_word, pad_pos, V, P, NTY, kd, thr, kss);
+    };
+    if (det == nullptr) { go(f32_embed_bwd_kernel<C, false>); return; }
+    go(f32_embed_bwd_kernel<C, true>);
+    // one table at a time through the same scratch (stream order): sort by the table's key, sum the runs, complete
+    // the runs that cross chunks.  The type table only when its rows are not the block partials (NTY > 2).
+    const int nwb = (hq_f32_embed_run_chunks(T) + kW - 1) / kW;
+    auto table = [&](auto run, const int64_t* keys, int NK, float* g_dst, int pad_key) {
+      hq_sort_ids(keys, T, NK, det->keys, det->rows, det->skeys, det->srows, det->sort_tmp, det->sort_bytes, s);
+      hipLaunchKernelGGL(run, dim3(nwb), dim3(256), 0, s, det->skeys, det->srows, dy, ids, pids, tids, ww, wp, wt, gamma,
+                         mean, rstd, g_dst, det->carry, T, H, pad_key, accumulate ? 1 : 0, NK, V, P, NTY, kd, thr, kss);
+      hipLaunchKernelGGL(f32_embed_carry_kernel<C>, dim3(nwb), dim3(256), 0, s, det->skeys, det->carry, g_dst, T, H,
+                         pad_key, accumulate ? 1 : 0, NK);
+    };
+    table(f32_embed_run_kernel<C, 0>, ids, V, g_word, pad_word);
+    table(f32_embed_run_kernel<C, 1>, pids, P, g_pos, pad_pos);
+    if (NTY > 2) table(f32_embed_run_kernel<C, 2>, tids, NTY, g_type, -1);
   });
   fold(part, nb, H, 4, outs, accumulate, s);
 }

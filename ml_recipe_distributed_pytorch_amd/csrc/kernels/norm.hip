@@ -11,7 +11,8 @@
 // Layout: one wave per row; lane owns 4 consecutive columns per 256-column chunk (8-byte bf16
 // vector access), NCH = ceil(H/256) chunks.  Column partial sums are reduced per block through
 // LDS and finished by hq_colsum (one 1024-thread block per 64 columns), so every gradient is
-// bitwise deterministic (position ids other than 0 … L-1 fall back to float atomics for the position rows).
+// bitwise deterministic (position ids other than 0 … L-1 and more than 2 types scatter those rows with float
+// atomics by default; hq_embed_bwd's det_pos / det_type modes sum them over pid- / tid-sorted runs instead).
 
 #include "hq_common.h"
 #include "hq_kernels.h"
@@ -460,7 +461,10 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
 //   4. embed_carry_kernel: the chunk where a crossing run starts adds its pieces in chunk order.
 // Every sum has a fixed order, so the result is bitwise reproducible (the round-4 kernel scattered 75 M f32
 // atomics into the word gradients: 316 µs at T = 98304 and run-to-run different low bits).
-// Position ids other than l (RoBERTa's l + 2, user-supplied ids) fall back to f32 atomics for those rows.
+// Position ids other than l (RoBERTa's, user-supplied ids) fall back to f32 atomics for those rows by default, as
+// do the type rows of more than 2 types.  The caller-selected deterministic modes remove both: det_pos runs
+// embed_bwd_kernel without any position work and takes every position gradient from a sort of the position ids
+// plus the position instantiation of steps 3-4; det_type does the same for the type rows with the type ids.
 //
 // part layout per block: [gamma | beta | type0 | type1] × H
 //
@@ -468,7 +472,7 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* __restric
 // kEmbNB batch rows b = y·kEmbNB … (row = b·L + l).  The next row's dy / embedding rows / statistics are
 // loaded while the current row is reduced (one dependent HBM round trip per row otherwise).
 constexpr int kEmbNB = 16;       // batch rows per wave in the position pass (<= 64, as kEmbCH)
-constexpr int kEmbCH = 16;       // sorted rows per wave in the word pass (<= 64: one row's metadata per lane)
+constexpr int kEmbCH = kHqEmbRunChunk;   // sorted rows per wave in the sorted-run pass (16; <= 64: one row's metadata per lane)
 constexpr int kEmbMaxL = 4096;   // position partials [T / L / kEmbNB][min(L, P)][H] only for real sequence layouts
 
 template <int NCH>
@@ -562,7 +566,10 @@ __device__ __forceinline__ void emb_gamma(const float* __restrict__ gamma, int H
   }
 }
 
-template <int NCH>
+// NOPOS (deterministic-positions mode): no position work at all — no partial rows, no flushes; the position
+// gradients come from the position instantiation of embed_word_kernel.  NOTYPE: likewise no type atomics at
+// n_types > 2 (the type instantiation).  <NCH, false, false> is the kernel as it always was.
+template <int NCH, bool NOPOS = false, bool NOTYPE = false>
 __global__ __launch_bounds__(256) void embed_bwd_kernel(
     const uint16_t* __restrict__ dy, const int64_t* __restrict__ ids, const int64_t* __restrict__ pids,
     const int64_t* __restrict__ tids, const uint16_t* __restrict__ ww, const uint16_t* __restrict__ wp,
@@ -589,7 +596,7 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(
   const int l = blockIdx.x * kWaves + wave;
   // this wave's position-partial row [blockIdx.y][l] (l < PL = min(L, P): pid == l needs l < P; ppart = null:
   // every position flush is atomic)
-  float* prow = (ppart != nullptr && l < PL) ? ppart + ((size_t)blockIdx.y * PL + l) * H : nullptr;
+  float* prow = (!NOPOS && ppart != nullptr && l < PL) ? ppart + ((size_t)blockIdx.y * PL + l) * H : nullptr;
   // the partial rows are [ceil(B / kEmbNB)][PL][H] with PL = min(L, P): row l exists only for l < PL (77ab202: the
   // flat layout, L = T > P, once wrote rows past the buffer)
   HQ_DASSERT(prow == nullptr || (l < PL && PL <= P && (int)blockIdx.y < (B + kEmbNB - 1) / kEmbNB));
@@ -637,7 +644,7 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(
     HQ_DASSERT(cur.id >= 0 && cur.id < V && pid >= 0 && pid < P && tid >= 0 && tid < n_types);
     float g[NCH][4], xh[NCH][4], dx[NCH][4];
     emb_row_grad<NCH>(cur, row * H, gam, key, thr, kscale, H, lane, g, xh, dx);
-    if ((int)pid != pcur) {  // wave-uniform: the running position sum belongs to another position
+    if (!NOPOS && (int)pid != pcur) {  // wave-uniform: the running position sum belongs to another position
       flush_pos();
       pcur = (int)pid;
     }
@@ -650,7 +657,7 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(
         for (int i = 0; i < 4; ++i) {
           acc[0][c][i] += g[c][i] * xh[c][i];
           acc[1][c][i] += g[c][i];
-          pacc[c][i] += dx[c][i];
+          if (!NOPOS) pacc[c][i] += dx[c][i];
         }
         if (n_types <= 2) {  // static indices only: acc[2 + (tid & 1)] put the whole array in scratch memory
 #pragma unroll
@@ -658,14 +665,14 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(
             acc[2][c][i] += t1 ? 0.f : dx[c][i];
             acc[3][c][i] += t1 ? dx[c][i] : 0.f;
           }
-        } else {
+        } else if (!NOTYPE) {
 #pragma unroll
           for (int i = 0; i < 4; ++i) atomicAdd(g_type + (size_t)tid * H + col + i, dx[c][i]);
         }
       }
     }
   }
-  flush_pos();
+  if (!NOPOS) flush_pos();
   if (prow != nullptr && !pstored) {   // no row at position l in this batch slice: a zero partial
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
@@ -806,7 +813,11 @@ __global__ __launch_bounds__(256) void sort_scatter_kernel(const int64_t* __rest
 // the chunk's FIRST run when it continues from chunk c-1 → carry slot 0 of c; the chunk's LAST run when it
 // continues into chunk c+1 and began in this chunk → carry slot 1 of c (a run covering the whole chunk from
 // both sides is slot 0).  embed_carry_kernel completes the crossing runs.  Padding ids get no gradient.
-template <int NCH>
+// KEY picks the id the rows were sorted by and with it the table (0: word ids -> g_word, 1: position ids -> g_pos in
+// the deterministic-positions mode, 2: type ids -> g_type at n_types > 2); g_word / pad_word / V are then that
+// table's gradient, skipped key and row count.  Summation order of a row: the rows of one key inside one chunk (a
+// piece) from zero in token order, the pieces of a crossing run in chunk order, the existing row (accumulate) last.
+template <int NCH, int KEY = 0>
 __global__ __launch_bounds__(256) void embed_word_kernel(
     const int32_t* __restrict__ skeys, const int32_t* __restrict__ srows, const uint16_t* __restrict__ dy,
     const int64_t* __restrict__ ids, const int64_t* __restrict__ pids, const int64_t* __restrict__ tids,
@@ -865,8 +876,8 @@ __global__ __launch_bounds__(256) void embed_word_kernel(
     cur = nxt;
     if (j + 1 < j1)
       emb_load_k<NCH>(nxt, meta, j + 1 - j0, (size_t)__builtin_amdgcn_readlane(myrow, j + 1 - j0), dy, ww, wp, wt, H, lane);
-    const int id = (int)cur.id;
-    HQ_DASSERT(id >= 0 && id < V && row < (size_t)T);
+    const int id = (int)(KEY == 0 ? cur.id : (KEY == 1 ? cur.pid : cur.tid));   // the row's key
+    HQ_DASSERT(id >= 0 && id < V && row < (size_t)T && id == skeys[j]);
     if (id != seg) {
       flush(seg, seg_first && head_cont ? 0 : 2);
       seg = id;
@@ -877,7 +888,12 @@ __global__ __launch_bounds__(256) void embed_word_kernel(
 #pragma unroll
     for (int q = 0; q < NCH; ++q)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) acc[q][i] += dx[q][i];
+      for (int i = 0; i < 4; ++i) {
+        // a plain add of the row's rounded dx (never a multiply fused into the running sum): the piece is the
+        // sum of its rows' dx, which is the documented order
+#pragma clang fp contract(off)
+        acc[q][i] += dx[q][i];
+      }
   }
   const bool from_prev = seg_first && head_cont;
   flush(seg, from_prev ? 0 : (after == seg ? 1 : 2));
@@ -1288,7 +1304,7 @@ void hq_embed_bwd(const uint16_t* dy, const int64_t* ids, const int64_t* pids, c
                   const uint16_t* wp, const uint16_t* wt, const float* gamma, const float* mean, const float* rstd,
                   float* g_word, float* g_pos, float* g_type, float* part, HqOuts outs, int T, int H,
                   int n_types, int pad_word, int pad_pos, float p, uint32_t seed, uint32_t opid, bool accumulate,
-                  int V, int P, int L, const HqEmbScratch& sc, hipStream_t s) {
+                  int V, int P, int L, const HqEmbScratch& sc, hipStream_t s, bool det_pos, bool det_type) {
   const uint32_t thr = p > 0.f ? hq_threshold(p) : 0u;
   const HqDropKey key = hq_drop_key(seed, opid);
   const float ks = hq_keep_scale(thr);
@@ -1298,19 +1314,37 @@ void hq_embed_bwd(const uint16_t* dy, const int64_t* ids, const int64_t* pids, c
   const int nb = hq_embed_bwd_partials(T, L);
   const HqEmbScratchSizes z = hq_embed_bwd_scratch(T, V, L, P);
   const int PL = std::min(L, P);   // position-partial rows per batch slice
-  float* ppart = z.pos_rows > 0 ? sc.ppart : nullptr;
+  float* ppart = (z.pos_rows > 0 && !det_pos) ? sc.ppart : nullptr;
+  det_type = det_type && n_types > 2;   // n_types <= 2: the type rows are block partials, no atomics to replace
   // (id, row) sort: the own stable radix sort, so every id's rows stay in token order
   hq_sort_ids(ids, T, V, sc.keys, sc.rows, sc.skeys, sc.srows, sc.sort_tmp, sc.sort_bytes, s);
   const int nwb = (z.chunks + kWaves - 1) / kWaves;
   dispatch_nch(H, [&](auto nch) {
     constexpr int C = decltype(nch)::value;
-    hipLaunchKernelGGL(embed_bwd_kernel<C>, grid, dim3(256), 4 * H * sizeof(float), s, dy, ids, pids, tids, ww, wp, wt,
-                       gamma, mean, rstd, g_pos, g_type, ppart, part, T, H, n_types, pad_pos, key, thr, ks, V, P, B, L,
-                       PL);
-    hipLaunchKernelGGL(embed_word_kernel<C>, dim3(nwb), dim3(256), 0, s, sc.skeys, sc.srows, dy, ids, pids, tids, ww,
-                       wp, wt, gamma, mean, rstd, g_word, sc.carry, T, H, pad_word, accumulate ? 1 : 0, key, thr, ks, V);
-    hipLaunchKernelGGL(embed_carry_kernel<C>, dim3(nwb), dim3(256), 0, s, sc.skeys, sc.carry, g_word, T, H, pad_word,
-                       accumulate ? 1 : 0, V);
+    auto bwd = [&](auto kern) {
+      hipLaunchKernelGGL(kern, grid, dim3(256), 4 * H * sizeof(float), s, dy, ids, pids, tids, ww, wp, wt, gamma, mean,
+                         rstd, g_pos, g_type, ppart, part, T, H, n_types, pad_pos, key, thr, ks, V, P, B, L, PL);
+    };
+    if (det_pos) { if (det_type) bwd(embed_bwd_kernel<C, true, true>); else bwd(embed_bwd_kernel<C, true, false>); }
+    else if (det_type) bwd(embed_bwd_kernel<C, false, true>);
+    else bwd(embed_bwd_kernel<C>);
+    // the rows sorted by one table's key: sum the runs, complete the runs that cross chunks
+    auto table = [&](auto run, float* g_dst, int pad_key, int NK) {
+      hipLaunchKernelGGL(run, dim3(nwb), dim3(256), 0, s, sc.skeys, sc.srows, dy, ids, pids, tids, ww, wp, wt, gamma, mean,
+                         rstd, g_dst, sc.carry, T, H, pad_key, accumulate ? 1 : 0, key, thr, ks, NK);
+      hipLaunchKernelGGL(embed_carry_kernel<C>, dim3(nwb), dim3(256), 0, s, sc.skeys, sc.carry, g_dst, T, H, pad_key,
+                         accumulate ? 1 : 0, NK);
+    };
+    table(embed_word_kernel<C>, g_word, pad_word, V);
+    // deterministic modes: the same sort scratch and carry rows, one table after the other (stream order)
+    if (det_pos) {
+      hq_sort_ids(pids, T, P, sc.keys, sc.rows, sc.skeys, sc.srows, sc.sort_tmp, sc.sort_bytes, s);
+      table(embed_word_kernel<C, 1>, g_pos, pad_pos, P);
+    }
+    if (det_type) {
+      hq_sort_ids(tids, T, n_types, sc.keys, sc.rows, sc.skeys, sc.srows, sc.sort_tmp, sc.sort_bytes, s);
+      table(embed_word_kernel<C, 2>, g_type, -1, n_types);
+    }
   });
   // outs: gamma, beta, type0, type1 (type rows only when n_types <= 2)
   colsum(part, nb, 4 * H, outs, H, accumulate, s);

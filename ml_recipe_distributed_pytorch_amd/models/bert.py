@@ -122,6 +122,9 @@ class _Ctx:
         self.head_mask = None   # [layers, H] per-column multipliers (each head's mask over its dh columns), or None
         # grad mode of the CALLER: inside an autograd.Function's forward torch.is_grad_enabled() is always False
         self.grad = torch.is_grad_enabled()
+        # the position ids are BERT's cached default ones (0 … L-1 per row): their gradient needs no scatter
+        # (ops.embed_bwd default_positions); False for RoBERTa and for caller-supplied position_ids
+        self.default_pos = True
 
 
 class _EmbeddingFn(torch.autograd.Function):
@@ -157,7 +160,8 @@ class _EmbeddingFn(torch.autograd.Function):
                           st.view(e + "word_embeddings.weight", "grad"), st.view(e + "position_embeddings.weight", "grad"),
                           st.view(e + "token_type_embeddings.weight", "grad"), st.view(e + "LayerNorm.weight", "grad"),
                           st.view(e + "LayerNorm.bias", "grad"), acc, m.config.pad_token_id,
-                          m.config.pad_token_id if m.config.family == "roberta" else -1, info.L)
+                          m.config.pad_token_id if m.config.family == "roberta" else -1, info.L,
+                          default_positions=info.default_pos)
             m._group_ready("embeddings")
         return None, None, None, None, None
 
@@ -731,6 +735,7 @@ class BertForQuestionAnswering(nn.Module):
         enc_train = self.transformer.training
         seed = int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) if (enc_train or self.classifier.training) else 0
         info = _Ctx(B, L, seed, enc_train, self)
+        info.default_pos = position_ids is None and self.config.family != "roberta"
         if head_mask is not None:
             info.head_mask = self._head_mask_columns(head_mask)
         anchor_e = self.store.params["transformer.embeddings.word_embeddings.weight"]

@@ -42,16 +42,22 @@ def embed_fwd(ids, pos_ids, type_ids, w_word, w_pos, w_type, gamma, beta, eps, p
 
 
 def embed_bwd(dy, ids, pos_ids, type_ids, w_word, w_pos, w_type, gamma, mean, rstd, p, seed, opid,
-              g_word, g_pos, g_type, g_gamma, g_beta, accumulate, pad_word=-1, pad_pos=-1, seq_len=0):
+              g_word, g_pos, g_type, g_gamma, g_beta, accumulate, pad_word=-1, pad_pos=-1, seq_len=0,
+              default_positions=True):
     """``seq_len`` = L of the [B, L] token layout (0: unknown) — lets the kernel walk one position across
-    the batch and sum the position-embedding gradient in registers."""
+    the batch and sum the position-embedding gradient in registers.  ``default_positions=False``: the caller's
+    position ids are not each row's column index (RoBERTa, user-supplied ``position_ids``); under
+    ``deterministic()`` the bf16 / fp8 kernel then sums every position gradient over pid-sorted runs instead of
+    scattering those rows with float atomics.  The fp32 kernels take the sorted path for every table whenever
+    ``deterministic()`` is true."""
     if _hip(dy):
+        det = deterministic()
         return _k().embed_bwd(dy, ids, pos_ids, type_ids, w_word, w_pos, w_type, gamma, mean, rstd, float(p),
                               int(seed), int(opid), g_word, g_pos, g_type, g_gamma, g_beta, bool(accumulate),
-                              int(pad_word), int(pad_pos), int(seq_len))
+                              int(pad_word), int(pad_pos), int(seq_len), det, det and not default_positions)
     if f32.active(dy):
         return f32.embed_bwd(dy, ids, pos_ids, type_ids, w_word, w_pos, w_type, gamma, mean, rstd, p, seed, opid,
-                             g_word, g_pos, g_type, g_gamma, g_beta, accumulate, pad_word, pad_pos)
+                             g_word, g_pos, g_type, g_gamma, g_beta, accumulate, pad_word, pad_pos, deterministic())
     return ref.embed_bwd(dy, ids, pos_ids, type_ids, w_word, w_pos, w_type, gamma, mean, rstd, p, seed, opid,
                          g_word, g_pos, g_type, g_gamma, g_beta, accumulate, pad_word, pad_pos)
 
@@ -138,9 +144,13 @@ def attn_fwd(qkv, key_bias, B, L, nh, p, seed, opid, scale):
 
 def deterministic() -> bool:
     """Bitwise run-to-run reproducible kernels wanted: ``torch.use_deterministic_algorithms(True)`` or
-    ``HQ_DETERMINISTIC=1``.  Only the attention backward has a faster order-nondeterministic path (the
-    single-kernel backward sums dQ over key slices with LDS float atomics); the embedding-gradient
-    scatter stays atomic either way."""
+    ``HQ_DETERMINISTIC=1``.  Two ops have a faster order-nondeterministic default that this turns off:
+    the attention backward (the single-kernel backward sums dQ over key slices with LDS float atomics) and the
+    embedding backward's float-atomic scatters — the whole fp32 backward (word, position and >2-type rows), and
+    in bf16 / fp8 the position rows of non-default position ids (RoBERTa, ``position_ids=``) and the type rows
+    of more than 2 types.  With it on, those gradients are summed over key-sorted runs in a fixed order
+    (``embed_bwd``) and no float atomic is reachable in ``csrc/kernels``.  bf16 / fp8 word gradients and BERT's
+    default-position gradients never use atomics."""
     return torch.are_deterministic_algorithms_enabled() or os.environ.get("HQ_DETERMINISTIC", "0") == "1"
 
 

@@ -70,11 +70,12 @@ def embed_fwd(ids, pos_ids, type_ids, w_word, w_pos, w_type, gamma, beta, eps, p
 
 
 def embed_bwd(dy, ids, pos_ids, type_ids, w_word, w_pos, w_type, gamma, mean, rstd, p, seed, opid,
-              g_word, g_pos, g_type, g_gamma, g_beta, accumulate, pad_word=-1, pad_pos=-1):
+              g_word, g_pos, g_type, g_gamma, g_beta, accumulate, pad_word=-1, pad_pos=-1, deterministic=False):
+    """``deterministic``: table gradients over key-sorted runs in a fixed order instead of f32 atomics."""
     kernels().f32_embed_bwd(dy.contiguous(), ids.contiguous(), pos_ids.contiguous(), type_ids.contiguous(),
                             w_word.contiguous(), w_pos.contiguous(), w_type.contiguous(), gamma.contiguous(), mean, rstd,
                             float(p), int(seed), int(opid), g_word, g_pos, g_type, g_gamma, g_beta, bool(accumulate),
-                            int(pad_word), int(pad_pos))
+                            int(pad_word), int(pad_pos), bool(deterministic))
 
 
 def ln_fwd(a, resid, gamma, beta, eps, p, seed, opid):
