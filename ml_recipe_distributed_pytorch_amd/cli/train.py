@@ -33,7 +33,8 @@ def _raise_interrupt(signum, frame):
 
 def build_trainer(params, model_params, device, *, rank: int, local_idx: int, use_gpu: bool) -> Trainer:
     model, tokenizer = factories.init_model(model_params, device=device, bpe_dropout=params.bpe_dropout,
-                                            seed=params.seed, precision=params.precision)
+                                            seed=params.seed, precision=params.precision,
+                                            fp32_matmul=params.fp32_matmul)
     optimizer = factories.init_optimizer(params, model)
     auto = getattr(params, "auto_batch_split", None)
     merge_segments = 1
@@ -91,7 +92,7 @@ def build_trainer(params, model_params, device, *, rank: int, local_idx: int, us
                    bucket_cap_mb=params.bucket_cap_mb, allreduce_dtype=params.allreduce_dtype,
                    no_sync_accum=bool(params.no_sync_accum), log_every=params.log_every, profile=params.profile,
                    cuda_graph=bool(getattr(params, "cuda_graph", False)),
-                   eval_shard=params.eval_shard, precision=params.precision,
+                   eval_shard=params.eval_shard, precision=params.precision, fp32_matmul=params.fp32_matmul,
                    torch_profile_dir=params.torch_profile_dir, torch_profile_steps=params.torch_profile_steps,
                    sampler_seed=params.seed if params.seed is not None else 0, merge_segments=merge_segments)
 

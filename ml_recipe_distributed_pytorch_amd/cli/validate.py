@@ -42,7 +42,9 @@ def main(params, model_params) -> Predictor:
     if params.checkpoint is not None and not os.path.exists(params.checkpoint):
         raise FileNotFoundError(f"Checkpoint {params.checkpoint} does not exist.")
     model, tokenizer = factories.init_model(model_params, checkpoint=params.checkpoint, device=device,
-                                            precision=params.precision)
+                                            precision=params.precision, fp32_matmul=params.fp32_matmul)
+    logger.info(f"Precision: {model.precision}, fp32 matmul: "
+                f"{factories.apply_fp32_matmul(params.fp32_matmul, model.precision)}.")
     dataset = get_validation_dataset(params, tokenizer=tokenizer)
     predictor = Predictor(model, device, collate_fun=factories.init_collate_fun(tokenizer, return_items=True),
                           batch_size=params.batch_size, n_jobs=params.n_jobs, buffer_size=params.buffer_size,

@@ -280,8 +280,10 @@ void f32_span_check(const Tensor& t, const char* name, std::initializer_list<std
 
 void gemm_f32(Tensor A, Tensor B, Tensor C, int64_t M, int64_t N, int64_t K, std::vector<int64_t> sa,
               std::vector<int64_t> sb, std::vector<int64_t> sc, int64_t batch, int64_t nb_in, double alpha,
-              c10::optional<Tensor> bias, c10::optional<Tensor> R, int64_t ldr) {
+              c10::optional<Tensor> bias, c10::optional<Tensor> R, int64_t ldr, const std::string& mode) {
   // sa = {sa_i, sa_k, ba_out, ba_in}, sb = {sb_j, sb_k, bb_out, bb_in}, sc = {ldc, bc_out, bc_in}
+  // mode: "exact" (f32-input MFMA) or "bf16x3" (three bf16 MFMAs over a hi + mid split of each operand)
+  TORCH_CHECK(mode == "exact" || mode == "bf16x3", "gemm_f32: mode must be 'exact' or 'bf16x3', got '", mode, "'");
   TORCH_CHECK(sa.size() == 4 && sb.size() == 4 && sc.size() == 3, "gemm_f32: stride vectors");
   TORCH_CHECK(M > 0 && N > 0 && K > 0 && batch >= 1 && nb_in >= 1 && batch % nb_in == 0, "gemm_f32: bad sizes");
   TORCH_CHECK(M * N < (int64_t)1 << 31 && K < (int64_t)1 << 31, "gemm_f32: sizes exceed 32-bit tile indexing");
@@ -310,10 +312,11 @@ void gemm_f32(Tensor A, Tensor B, Tensor C, int64_t M, int64_t N, int64_t K, std
   c10::DeviceGuard g(A.device());
   const int ks = hq_gemm_f32_splits((int)M, (int)N, (int)K, (int)batch);
   Tensor ws = ks > 1 ? at::empty({ks, M, N}, C.options()) : Tensor();
-  hq_gemm_f32(ptr<float>(A), ptr<float>(B), ptr<float>(C), has_b ? ptr<float>(*bias) : nullptr,
-              has_r ? ptr<float>(*R) : nullptr, ks > 1 ? ptr<float>(ws) : nullptr, (int)M, (int)N, (int)K, sa[0], sa[1],
-              sb[0], sb[1], (int)sc[0], (int)ldr, (int)batch, (int)nb_in, sa[2], sa[3], sb[2], sb[3], sc[1], sc[2],
-              (float)alpha, ks, cur_stream());
+  const auto launch = mode == "bf16x3" ? hq_gemm_f32x3 : hq_gemm_f32;
+  launch(ptr<float>(A), ptr<float>(B), ptr<float>(C), has_b ? ptr<float>(*bias) : nullptr,
+         has_r ? ptr<float>(*R) : nullptr, ks > 1 ? ptr<float>(ws) : nullptr, (int)M, (int)N, (int)K, sa[0], sa[1],
+         sb[0], sb[1], (int)sc[0], (int)ldr, (int)batch, (int)nb_in, sa[2], sa[3], sb[2], sb[3], sc[1], sc[2],
+         (float)alpha, ks, cur_stream());
 }
 
 // fp8 weight gradient: out [N,K] f32 (+)= (dy8ᵀ·x8)·sa·sb, dy8 e5m2 [T,N], x8 e4m3 [T,K] (token-major)
@@ -1008,7 +1011,8 @@ PYBIND11_MODULE(_hq_kernels, m) {
   m.def("gemm_tn_splits", &gemm_tn_splits);
   m.def("gemm_f32", &gemm_f32, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("M"), py::arg("N"), py::arg("K"),
         py::arg("sa"), py::arg("sb"), py::arg("sc"), py::arg("batch") = 1, py::arg("nb_in") = 1, py::arg("alpha") = 1.0,
-        py::arg("bias") = py::none(), py::arg("R") = py::none(), py::arg("ldr") = 0);
+        py::arg("bias") = py::none(), py::arg("R") = py::none(), py::arg("ldr") = 0,
+        py::arg("mode") = "exact");
   m.def("attn_set_force_slow", [](int64_t v) { hq_attn_set_force_slow((int)v); });
   m.def("transpose_tiles", &transpose_tiles);
   m.def("transpose_tiles8", &transpose_tiles8);

@@ -199,6 +199,12 @@ void hq_gemm_f32(const float* A, const float* B, float* C, const float* bias, co
                  int K, long long sa_i, long long sa_k, long long sb_j, long long sb_k, int ldc, int ldr, int batch,
                  int nb_in, long long ba_out, long long ba_in, long long bb_out, long long bb_in, long long bc_out,
                  long long bc_in, float alpha, int ksplit, hipStream_t s);
+// The same contract on the bf16 matrix cores (gemm_f32.hip, HQ_F32_MATMUL=bf16x3): each fp32 operand split into
+// two bf16 (hi + mid), C ≈ Amid·Bhi + Ahi·Bmid + Ahi·Bhi with an fp32 accumulator, error ≤ 3·2⁻¹⁶·Σ|a||b|.
+void hq_gemm_f32x3(const float* A, const float* B, float* C, const float* bias, const float* R, float* ws, int M, int N,
+                   int K, long long sa_i, long long sa_k, long long sb_j, long long sb_k, int ldc, int ldr, int batch,
+                   int nb_in, long long ba_out, long long ba_in, long long bb_out, long long bb_in, long long bc_out,
+                   long long bc_in, float alpha, int ksplit, hipStream_t s);
 
 // Weight-gradient GEMM (gemm_tn.hip): out[N,K] (+)= Aᵀ·B, A = dy [T,N] bf16, B = x [T,K] bf16 (token-major),
 // split-K over T into S fp32 slabs part[S][N][K] (caller-provided) reduced into out; with bout != null

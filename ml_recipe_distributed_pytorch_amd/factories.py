@@ -50,8 +50,20 @@ def init_tokenizer(model_params, *, bpe_dropout=None):
     return SpecialIds(cfg.vocab_size, cfg.pad_token_id, cfg.unk_token_id, cfg.cls_token_id, cfg.sep_token_id, family)
 
 
+def apply_fp32_matmul(mode: Optional[str], precision: Optional[str], warn: bool = True) -> str:
+    """``--fp32_matmul``: select the fp32 mode's projection GEMM (``None`` keeps the HQ_F32_MATMUL / default
+    setting) and return the mode in force.  It acts on fp32 compute only; with another precision it is inert."""
+    from .ops import f32
+    if mode is not None:
+        f32.set_matmul(mode)
+        if warn and precision != "fp32":
+            logger.warning(f"--fp32_matmul {mode} has no effect with precision {precision}: it selects the "
+                           f"projection GEMM of --precision fp32 only.")
+    return f32.MATMUL
+
+
 def init_model(model_params, *, checkpoint=None, device=torch.device("cpu"), bpe_dropout=None, seed=None,
-               precision: Optional[str] = None):
+               precision: Optional[str] = None, fp32_matmul: Optional[str] = None):
     model_params.model_name = "roberta" if model_params.model.startswith("roberta") else "bert"
     tokenizer = init_tokenizer(model_params, bpe_dropout=bpe_dropout)
     cfg = get_config(model_params.model, hidden_dropout_prob=model_params.hidden_dropout_prob,
@@ -60,6 +72,8 @@ def init_model(model_params, *, checkpoint=None, device=torch.device("cpu"), bpe
     if hasattr(tokenizer, "__len__") and len(tokenizer) > cfg.vocab_size:
         cfg.vocab_size = len(tokenizer)
     prec = precision or ("bf16" if torch.device(device).type == "cuda" else "fp32")
+    # applied before the model is built; the trainer resolves the final precision (apex_level) and warns there
+    apply_fp32_matmul(fp32_matmul, prec, warn=False)
     model = BertForQuestionAnswering(cfg, precision=prec, seed=seed)
     pre = getattr(model_params, "pretrained_path", None)
     if pre and getattr(model_params, "random_init", False):

@@ -10,12 +10,39 @@ softmax forward, LSE backward — no [B, nh, L, L] tensor at any length), and th
 (embedding gathers + LayerNorm, residual + dropout + LayerNorm, GELU, the bias-gradient column sums) are own fp32
 kernels too, with the dropout masks of ``ops.rng`` — so the fp32 GPU model reproduces the CPU oracle op for op.
 This mode exists for numerical parity with the reference's fp32 training; the bf16 / fp8 paths are the fast ones.
+
+``MATMUL`` (``HQ_F32_MATMUL`` / ``--fp32_matmul``, default ``exact``) selects how the encoder projections multiply:
+``"bf16x3"`` runs them on the bf16 matrix cores as three products of a two-term bf16 split of each fp32 operand
+(``gemm_f32x3_kernel``: error ≤ 3·2⁻¹⁶·Σ|a||b| — two digits better than bf16 inputs, two worse than exact; the
+analogue of TF32 / ``torch.set_float32_matmul_precision("high")``, which gfx950 has no instruction for).  Everything
+else of the fp32 mode — attention, LayerNorm, GELU, heads, optimizer, master weights — stays exact fp32, and
+``ops.reference`` follows the switch, so the CPU path remains the op-for-op oracle.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 
 from .._native import kernels
+
+MATMUL_MODES = ("exact", "bf16x3")
+
+
+def _check_mode(mode: str, where: str) -> str:
+    if mode not in MATMUL_MODES:
+        raise ValueError(f"{where}: fp32 matmul mode must be one of {MATMUL_MODES}, got {mode!r}")
+    return mode
+
+
+MATMUL = _check_mode(os.environ.get("HQ_F32_MATMUL", "exact"), "HQ_F32_MATMUL")
+
+
+def set_matmul(mode: str) -> str:
+    """Select the fp32 mode's projection GEMM (``"exact"`` | ``"bf16x3"``); returns the previous mode."""
+    global MATMUL
+    prev, MATMUL = MATMUL, _check_mode(mode, "set_matmul")
+    return prev
 
 
 def active(t: torch.Tensor) -> bool:
@@ -25,7 +52,7 @@ def active(t: torch.Tensor) -> bool:
 
 def _gemm(A, B, C, M, N, K, sa, sb, sc, batch=1, nb_in=1, alpha=1.0, bias=None, R=None, ldr=0):
     kernels().gemm_f32(A, B, C, int(M), int(N), int(K), [int(v) for v in sa], [int(v) for v in sb],
-                       [int(v) for v in sc], int(batch), int(nb_in), float(alpha), bias, R, int(ldr))
+                       [int(v) for v in sc], int(batch), int(nb_in), float(alpha), bias, R, int(ldr), mode=MATMUL)
     return C
 
 

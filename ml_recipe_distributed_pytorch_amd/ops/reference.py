@@ -16,6 +16,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from . import f32 as _f32
 from . import rng
 
 Tensor = torch.Tensor
@@ -179,23 +180,49 @@ def attn_bwd(dctx, qkv, ctx, lse, key_bias, B, L, nh, p, seed, opid, scale):
 
 
 # --------------------------------------------------------------------------------------- linear
+def split_bf16x3(x: Tensor) -> Tuple[Tensor, Tensor]:
+    """The two-term bf16 split of ``gemm_f32x3_kernel``: hi = bf16_rne(x), mid = bf16_rne(x − hi) (the subtraction
+    is exact in fp32), |x − hi − mid| ≤ 2⁻¹⁶·|x|.  Returned as bf16 tensors."""
+    x = x.float()
+    hi = x.to(torch.bfloat16)
+    mid = (x - hi.float()).to(torch.bfloat16)
+    return hi, mid
+
+
+def matmul_bf16x3(a: Tensor, b_t: Tensor) -> Tensor:
+    """a[M, K]·b_t[N, K]ᵀ as the fp32 mode's ``bf16x3`` GEMM computes it: the three leading products of the split
+    operands, the two small ones summed first.  Runs in the dtype of ``a`` (fp32; fp64 for the tests' oracle) —
+    every bf16·bf16 product is exact in either, so only the summation order over k differs from the kernel."""
+    dt = a.dtype if a.dtype == torch.float64 else torch.float32
+    ah, am = (t.to(dt) for t in split_bf16x3(a))
+    bh, bm = (t.to(dt).t() for t in split_bf16x3(b_t))
+    return (am @ bh + ah @ bm) + ah @ bh
+
+
+def _mm_t(a: Tensor, b_t: Tensor) -> Tensor:
+    """a·b_tᵀ in fp32; through the bf16x3 oracle for fp32 tensors while ``ops.f32.MATMUL`` selects that mode."""
+    if _f32.MATMUL == "bf16x3" and a.dtype == torch.float32 and b_t.dtype == torch.float32:
+        return matmul_bf16x3(a, b_t)
+    return a.float() @ b_t.float().t()
+
+
 def linear_fwd(x, w, b):
-    y = x.float() @ w.float().t()
+    y = _mm_t(x, w)
     if b is not None:
         y = y + b.float()
     return y.to(x.dtype)
 
 
 def linear_dgrad(dy, w):
-    return (dy.float() @ w.float()).to(dy.dtype)
+    return _mm_t(dy, w.t()).to(dy.dtype)
 
 
 def linear_dgrad_add(dy, w, resid):
-    return (resid.float() + dy.float() @ w.float()).to(dy.dtype)
+    return (resid.float() + _mm_t(dy, w.t())).to(dy.dtype)
 
 
 def linear_wgrad(dy, x, g_w, g_b, accumulate: bool):
-    _acc(g_w, dy.float().t() @ x.float(), accumulate)
+    _acc(g_w, _mm_t(dy.t(), x.t()), accumulate)
     if g_b is not None:
         _acc(g_b, dy.float().sum(0), accumulate)
 

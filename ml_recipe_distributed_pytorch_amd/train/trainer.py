@@ -124,6 +124,7 @@ class Trainer:
     cuda_graph: bool = False
     eval_shard: bool = False
     precision: Optional[str] = None
+    fp32_matmul: Optional[str] = None   # --fp32_matmul: exact | bf16x3 (None: HQ_F32_MATMUL, else exact)
     torch_profile_dir: Optional[str] = None
     torch_profile_steps: str = "3:5"
     sampler_seed: int = 0   # per-epoch sampler permutation = f(sampler_seed, epoch): reproducible on resume
@@ -157,7 +158,10 @@ class Trainer:
             logger.info(f"Warmup schedule is used. #Training steps: {num_training_steps}. "
                         f"#Warmup steps: {num_warmup_steps}.")
             self.scheduler = get_linear_schedule_with_warmup(self.optimizer, num_warmup_steps, num_training_steps)
-        logger.info(f"Precision: {prec} (apex_level {self.apex_level} mapped to native mixed precision).")
+        from ..factories import apply_fp32_matmul
+        matmul = apply_fp32_matmul(self.fp32_matmul, prec)   # warns when given with another precision
+        logger.info(f"Precision: {prec} (apex_level {self.apex_level} mapped to native mixed precision), "
+                    f"fp32 matmul: {matmul}.")
         self.reducer = None
         if self.world > 1 and self.optimizer is not None:
             self.reducer = GradReducer(self.model, bucket_cap_mb=self.bucket_cap_mb,

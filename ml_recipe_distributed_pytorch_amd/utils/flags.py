@@ -98,6 +98,10 @@ def init_base_arguments(parser: ArgumentParser) -> None:
     # --- MI355X additions (shared) ----------------------------------------------------------
     parser.add_argument("--precision", type=cast2(str), default=None, choices=[None, "fp32", "bf16", "fp8"],
                         help="Compute precision. Default: bf16 on GPU (apex O1/O2 map to bf16), fp32 on CPU.")
+    parser.add_argument("--fp32_matmul", type=cast2(str), default=None, choices=[None, "exact", "bf16x3"],
+                        help="Projection GEMMs of --precision fp32: exact (f32 matrix cores) or bf16x3 (three bf16 "
+                             "products of a two-term split of each operand, error <= 3*2^-16 of sum|a||b|; the "
+                             "analogue of TF32). Default: the HQ_F32_MATMUL environment variable, else exact.")
     parser.add_argument("--dummy_dataset_len", type=int, default=10000, help="Length of the dummy dataset.")
 
 
