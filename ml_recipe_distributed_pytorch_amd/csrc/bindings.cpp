@@ -21,17 +21,26 @@ void check(const Tensor& t, at::ScalarType dt, const char* name) {
   TORCH_CHECK(t.scalar_type() == dt, name, " has dtype ", t.scalar_type(), ", expected ", dt);
   TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
 }
+bool has(const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); }
 void check_opt(const c10::optional<Tensor>& t, at::ScalarType dt, const char* name) {
-  if (t.has_value() && t->defined()) check(*t, dt, name);
+  if (has(t)) check(*t, dt, name);
 }
 template <typename T>
 T* ptr(const Tensor& t) { return reinterpret_cast<T*>(t.data_ptr()); }
 template <typename T>
-T* optr(const c10::optional<Tensor>& t) { return (t.has_value() && t->defined()) ? reinterpret_cast<T*>(t->data_ptr()) : nullptr; }
+T* optr(const c10::optional<Tensor>& t) { return has(t) ? reinterpret_cast<T*>(t->data_ptr()) : nullptr; }
 
 const auto BF16 = at::kBFloat16;
 const auto F32 = at::kFloat;
 const auto I64 = at::kLong;
+
+// an fp8 site's f32[4] delayed-scaling state, checked (`what`: the error of a wrong size) -> the kernels' pointer
+float* state4(const c10::optional<Tensor>& t, const char* name, const char* what) {
+  if (!has(t)) return nullptr;
+  check(*t, F32, name);
+  TORCH_CHECK(t->numel() == 4, what);
+  return ptr<float>(*t);
+}
 
 HqOuts outs4(float* a, float* b = nullptr, float* c = nullptr, float* d = nullptr) { return HqOuts{{a, b, c, d}}; }
 
@@ -57,6 +66,20 @@ std::vector<Tensor> embed_fwd(Tensor ids, Tensor pids, Tensor tids, Tensor ww, T
                (int)T, (int)H, (float)eps, (float)p, u32(seed), u32(opid), (int)ww.size(0), (int)wp.size(0),
                (int)wt.size(0), cur_stream());
   return {y, mean, rstd};
+}
+
+// Scratch of the sorted-run table gradients (embed_bwd, f32_embed_bwd): the (key, row) pairs and their sorted copies,
+// sort_bytes of digit histograms, `chunks` pairs of carry rows.  The tensors own what `sc` points into.
+struct EmbScratch { Tensor pairs, sort_tmp, carry; HqEmbScratch sc{}; };
+EmbScratch emb_scratch(const Tensor& ids, const at::TensorOptions& f32, int64_t T, int64_t H, size_t sort_bytes,
+                       int64_t chunks, float* ppart) {
+  EmbScratch e;
+  e.pairs = at::empty({4, T}, ids.options().dtype(at::kInt));
+  e.sort_tmp = at::empty({(int64_t)std::max<size_t>(sort_bytes, 1)}, ids.options().dtype(at::kByte));
+  e.carry = at::empty({chunks * 2, H}, f32);
+  int32_t* pr = e.pairs.data_ptr<int32_t>();
+  e.sc = HqEmbScratch{pr, pr + T, pr + 2 * T, pr + 3 * T, e.sort_tmp.data_ptr(), sort_bytes, ptr<float>(e.carry), ppart};
+  return e;
 }
 
 void embed_bwd(Tensor dy, Tensor ids, Tensor pids, Tensor tids, Tensor ww, Tensor wp, Tensor wt, Tensor gamma, Tensor mean,
@@ -86,24 +109,19 @@ void embed_bwd(Tensor dy, Tensor ids, Tensor pids, Tensor tids, Tensor ww, Tenso
   auto part = at::empty({nb, 4 * H}, gamma.options());
   const int V = (int)ww.size(0);
   const HqEmbScratchSizes zs = hq_embed_bwd_scratch((int)T, V, (int)seq_len, (int)wp.size(0));
-  auto pairs = at::empty({4, T}, ids.options().dtype(at::kInt));
   // the position / type sorts of the deterministic modes reuse the word sort's scratch: room for the largest
   size_t sort_bytes = zs.sort_bytes;
   if (det_positions) sort_bytes = std::max(sort_bytes, hq_sort_ids_bytes((int)T, (int)wp.size(0)));
   if (deterministic && n_types > 2) sort_bytes = std::max(sort_bytes, hq_sort_ids_bytes((int)T, n_types));
-  auto sort_tmp = at::empty({(int64_t)std::max<size_t>(sort_bytes, 1)}, ids.options().dtype(at::kByte));
-  auto carry = at::empty({(int64_t)zs.chunks * 2, H}, gamma.options());
   auto ppart = at::empty({std::max<int64_t>(det_positions ? 0 : zs.pos_rows, 1), H}, gamma.options());
-  int32_t* pr = pairs.data_ptr<int32_t>();
-  const HqEmbScratch sc{pr, pr + T, pr + 2 * T, pr + 3 * T, sort_tmp.data_ptr(), sort_bytes, ptr<float>(carry),
-                        ptr<float>(ppart)};
+  const EmbScratch es = emb_scratch(ids, gamma.options(), T, H, sort_bytes, zs.chunks, ptr<float>(ppart));
   float* t0 = ptr<float>(g_type);
   HqOuts o = outs4(ptr<float>(g_gamma), ptr<float>(g_beta), n_types <= 2 ? t0 : nullptr,
                    n_types == 2 ? t0 + H : nullptr);
   hq_embed_bwd(ptr<uint16_t>(dy), ptr<int64_t>(ids), ptr<int64_t>(pids), ptr<int64_t>(tids), ptr<uint16_t>(ww),
                ptr<uint16_t>(wp), ptr<uint16_t>(wt), ptr<float>(gamma), ptr<float>(mean), ptr<float>(rstd),
                ptr<float>(g_word), ptr<float>(g_pos), t0, ptr<float>(part), o, (int)T, (int)H, n_types, (int)pad_word,
-               (int)pad_pos, (float)p, u32(seed), u32(opid), accumulate, V, (int)wp.size(0), (int)seq_len, sc, s,
+               (int)pad_pos, (float)p, u32(seed), u32(opid), accumulate, V, (int)wp.size(0), (int)seq_len, es.sc, s,
                det_positions, deterministic);
 }
 
@@ -113,19 +131,16 @@ void embed_bwd(Tensor dy, Tensor ids, Tensor pids, Tensor tids, Tensor ww, Tenso
 // store_z = false: z is not written (returned empty) — the backward then recomputes x̂ from y (ln_bwd beta=)
 std::vector<Tensor> ln_fwd(Tensor a, c10::optional<Tensor> resid_opt, Tensor gamma, Tensor beta, double eps, double p,
                            int64_t seed, int64_t opid, c10::optional<Tensor> q8, int64_t phase, bool store_z) {
-  const bool zin = !(resid_opt.has_value() && resid_opt->defined());
+  const bool zin = !has(resid_opt);
   check(a, BF16, "a"); check(gamma, F32, "gamma"); check(beta, F32, "beta");
   if (!zin) check(*resid_opt, BF16, "resid");
   TORCH_CHECK(a.dim() == 2 && (zin || a.sizes() == resid_opt->sizes()), "a/resid shape");
   const int64_t T = a.size(0), H = a.size(1);
   TORCH_CHECK(gamma.numel() == H && beta.numel() == H && H % 4 == 0 && H <= 2048, "hidden size");
   TORCH_CHECK(T * H < (int64_t)std::numeric_limits<uint32_t>::max(), "T*H exceeds 32-bit dropout index");
-  const bool want8 = q8.has_value() && q8->defined();
+  const bool want8 = has(q8);
   TORCH_CHECK(!(zin && want8), "ln_fwd: the z-in form has no e4m3 output");
-  if (want8) {
-    check(*q8, F32, "q8");
-    TORCH_CHECK(q8->numel() == 4, "q8 must be the f32[4] delayed-scaling state");
-  }
+  float* q8p = state4(q8, "q8", "q8 must be the f32[4] delayed-scaling state");
   c10::DeviceGuard g(a.device());
   auto y = at::empty_like(a);
   const bool wz = zin || store_z;
@@ -135,8 +150,7 @@ std::vector<Tensor> ln_fwd(Tensor a, c10::optional<Tensor> resid_opt, Tensor gam
   hq_ln_fwd(ptr<uint16_t>(a), zin ? nullptr : ptr<uint16_t>(*resid_opt), ptr<float>(gamma), ptr<float>(beta),
             ptr<uint16_t>(y), (zin || !wz) ? nullptr : ptr<uint16_t>(z),
             ptr<float>(mean), ptr<float>(rstd), (int)T, (int)H, (float)eps, (float)p, u32(seed), u32(opid), cur_stream(),
-            want8 ? reinterpret_cast<uint8_t*>(y8.data_ptr()) : nullptr, want8 ? ptr<float>(*q8) : nullptr,
-            (int)(phase % 3));
+            want8 ? reinterpret_cast<uint8_t*>(y8.data_ptr()) : nullptr, q8p, (int)(phase % 3));
   if (want8) return {y, z, mean, rstd, y8};
   return {y, z, mean, rstd};
 }
@@ -147,7 +161,7 @@ std::vector<Tensor> ln_bwd(Tensor dy, c10::optional<Tensor> dy2, Tensor z, Tenso
                            c10::optional<Tensor> g_bias, bool accumulate, c10::optional<Tensor> q8, int64_t phase,
                            bool write_da, c10::optional<Tensor> beta) {
   // beta given: `z` is the forward OUTPUT y and x̂ = (y − β)/γ (the forward ran with store_z = false)
-  const bool fromy = beta.has_value() && beta->defined();
+  const bool fromy = has(beta);
   if (fromy) {
     check(*beta, F32, "beta");
     TORCH_CHECK(beta->numel() == dy.size(1), "ln_bwd: beta length");
@@ -156,20 +170,19 @@ std::vector<Tensor> ln_bwd(Tensor dy, c10::optional<Tensor> dy2, Tensor z, Tenso
   check(mean, F32, "mean"); check(rstd, F32, "rstd");
   check_opt(g_gamma, F32, "g_gamma"); check_opt(g_beta, F32, "g_beta"); check_opt(g_bias, F32, "g_bias");
   TORCH_CHECK(dy.sizes() == z.sizes(), "dy/z shape");
-  if (dy2.has_value() && dy2->defined()) TORCH_CHECK(dy2->sizes() == dy.sizes(), "dy2 shape");
+  if (has(dy2)) TORCH_CHECK(dy2->sizes() == dy.sizes(), "dy2 shape");
   const int64_t T = dy.size(0), H = dy.size(1);
   TORCH_CHECK(gamma.numel() == H && mean.numel() == T && rstd.numel() == T, "stat shapes");
   c10::DeviceGuard g(dy.device());
   // write_da = false (with q8): da only as e5m2 — the bf16 da comes back empty
-  TORCH_CHECK(write_da || (q8.has_value() && q8->defined()), "ln_bwd: write_da=False needs q8");
+  TORCH_CHECK(write_da || has(q8), "ln_bwd: write_da=False needs q8");
   auto dz = at::empty_like(dy), da = write_da ? at::empty_like(dy) : at::empty({0}, dy.options());
   const int nb = hq_ln_bwd_partials((int)T);
   auto part = at::empty({nb, 3 * H}, gamma.options());
-  const bool want8 = q8.has_value() && q8->defined();
+  const bool want8 = has(q8);
+  float* q8p = state4(q8, "q8", "ln_bwd: q8 must be f32[4]");
   Tensor da8;
   if (want8) {
-    check(*q8, F32, "q8");
-    TORCH_CHECK(q8->numel() == 4, "ln_bwd: q8 must be f32[4]");
     TORCH_CHECK(H % 4 == 0, "ln_bwd: e5m2 output needs H % 4 == 0");
     da8 = at::empty(dy.sizes(), dy.options().dtype(at::kFloat8_e5m2));
   }
@@ -177,12 +190,11 @@ std::vector<Tensor> ln_bwd(Tensor dy, c10::optional<Tensor> dy2, Tensor z, Tenso
             ptr<uint16_t>(dz), write_da ? ptr<uint16_t>(da) : nullptr, ptr<float>(part),
             outs4(optr<float>(g_gamma), optr<float>(g_beta), optr<float>(g_bias)), (int)T, (int)H, (float)p, u32(seed),
             u32(opid), accumulate, cur_stream(), want8 ? reinterpret_cast<uint8_t*>(da8.data_ptr()) : nullptr,
-            want8 ? ptr<float>(*q8) : nullptr, (int)(phase % 3), fromy ? ptr<float>(*beta) : nullptr);
+            q8p, (int)(phase % 3), fromy ? ptr<float>(*beta) : nullptr);
   if (want8) return {dz, da, da8};
   return {dz, da};
 }
 
-// ------------------------------------------------------------------------------------------ GELU
 // ------------------------------------------------------------------------------------ MFMA GEMM
 // C[M,N] = A[M,K] · B[N,K]^T with epilogue `epi` (HQ_EPI_*).  bias f32[N] (BIAS/GELU); pre bf16[M,N]
 // (GELU: written, DGELU: read); resid bf16[M,N] (RESID); part f32[M/256, N] (DGELU column partials).
@@ -199,30 +211,30 @@ Tensor gemm_nt(Tensor A, Tensor B, int64_t epi, c10::optional<Tensor> bias, c10:
   TORCH_CHECK(bn > 0, "gemm_nt: unsupported shape M=", M, " N=", N, " K=", K, " (need N%128, K%64 == 0)");
   TORCH_CHECK(epi >= HQ_EPI_NONE && epi <= HQ_EPI_BDR, "gemm_nt: bad epilogue");
   if (epi == HQ_EPI_BDR) {
-    TORCH_CHECK(bias.has_value() && bias->defined(), "gemm_nt: EPI_BDR needs the fp32 bias");
+    TORCH_CHECK(has(bias), "gemm_nt: EPI_BDR needs the fp32 bias");
     TORCH_CHECK(M * N < (int64_t)std::numeric_limits<uint32_t>::max(), "gemm_nt: M*N exceeds 32-bit dropout index");
   }
   c10::DeviceGuard g(A.device());
-  Tensor C = (out.has_value() && out->defined()) ? *out : at::empty({M, N}, A.options());
+  Tensor C = has(out) ? *out : at::empty({M, N}, A.options());
   check(C, BF16, "out");
   TORCH_CHECK(C.size(0) == M && C.size(1) == N, "gemm_nt: out shape");
   if (epi == HQ_EPI_BIAS || epi == HQ_EPI_GELU || epi == HQ_EPI_GELUD) {
-    TORCH_CHECK(bias.has_value() && bias->defined(), "gemm_nt: bias required");
+    TORCH_CHECK(has(bias), "gemm_nt: bias required");
     check(*bias, F32, "bias");
     TORCH_CHECK(bias->numel() == N, "gemm_nt: bias length");
   }
   if (epi == HQ_EPI_GELU || epi == HQ_EPI_DGELU || epi == HQ_EPI_GELUD || epi == HQ_EPI_DMUL) {
-    TORCH_CHECK(pre.has_value() && pre->defined(), "gemm_nt: pre required");
+    TORCH_CHECK(has(pre), "gemm_nt: pre required");
     check(*pre, BF16, "pre");
     TORCH_CHECK(pre->size(0) == M && pre->size(1) == N, "gemm_nt: pre shape");
   }
   if (epi == HQ_EPI_RESID || epi == HQ_EPI_BDR) {
-    TORCH_CHECK(resid.has_value() && resid->defined(), "gemm_nt: resid required");
+    TORCH_CHECK(has(resid), "gemm_nt: resid required");
     check(*resid, BF16, "resid");
     TORCH_CHECK(resid->size(0) == M && resid->size(1) == N, "gemm_nt: resid shape");
   }
   if (epi == HQ_EPI_DGELU || epi == HQ_EPI_DMUL) {
-    TORCH_CHECK(part.has_value() && part->defined(), "gemm_nt: part required");
+    TORCH_CHECK(has(part), "gemm_nt: part required");
     check(*part, F32, "part");
     TORCH_CHECK(part->numel() == (int64_t)hq_gemm_nt_part_rows((int)M, (int)N, (int)K) * N,
                 "gemm_nt: part must hold [gemm_nt_part_rows(M, N, K), N]");
@@ -249,7 +261,7 @@ void gemm_tn(Tensor dy, Tensor x, Tensor out, bool accumulate, int64_t splits, c
   TORCH_CHECK(auto_s > 0, "gemm_tn: unsupported shape T=", T, " N=", N, " K=", K, " (need N%128, K%128 == 0, T >= 128)");
   const int S = splits > 0 ? (int)splits : auto_s;
   TORCH_CHECK((T + 63) / 64 / S >= 2, "gemm_tn: too many splits");
-  const bool has_bias = bias_out.has_value() && bias_out->defined();
+  const bool has_bias = has(bias_out);
   if (has_bias) {
     check(*bias_out, F32, "bias_out");
     TORCH_CHECK(bias_out->numel() == N, "gemm_tn: bias_out must hold N");
@@ -305,9 +317,9 @@ void gemm_f32(Tensor A, Tensor B, Tensor C, int64_t M, int64_t N, int64_t K, std
   f32_span_check(A, "A", {{M, sa[0]}, {K, sa[1]}, {nbo, sa[2]}, {nb_in, sa[3]}});
   f32_span_check(B, "B", {{N, sb[0]}, {K, sb[1]}, {nbo, sb[2]}, {nb_in, sb[3]}});
   f32_span_check(C, "C", {{M, sc[0]}, {N, 1}, {nbo, sc[1]}, {nb_in, sc[2]}});
-  const bool has_r = R.has_value() && R->defined();
+  const bool has_r = has(R);
   if (has_r) f32_span_check(*R, "R", {{M, ldr}, {N, 1}, {nbo, sc[1]}, {nb_in, sc[2]}});
-  const bool has_b = bias.has_value() && bias->defined();
+  const bool has_b = has(bias);
   if (has_b) { check(*bias, F32, "bias"); TORCH_CHECK(bias->numel() == N, "gemm_f32: bias must hold N"); }
   c10::DeviceGuard g(A.device());
   const int ks = hq_gemm_f32_splits((int)M, (int)N, (int)K, (int)batch);
@@ -362,13 +374,13 @@ Tensor gemm_fp8(Tensor A8, Tensor B8, int64_t epi, c10::optional<Tensor> bias, T
   check(sa, F32, "sa"); check(sb, F32, "sb");
   TORCH_CHECK(sa.numel() >= 1 && sb.numel() >= 1, "gemm_fp8: sa, sb");
   if (fwd) {
-    TORCH_CHECK(bias.has_value() && bias->defined(), "gemm_fp8: forward epilogues need the fp32 bias");
+    TORCH_CHECK(has(bias), "gemm_fp8: forward epilogues need the fp32 bias");
     check(*bias, F32, "bias");
     TORCH_CHECK(bias->numel() == N, "gemm_fp8: bias[N]");
   }
   c10::DeviceGuard g(A8.device());
   // write_out = false (GELUD / DMUL with out8): only the fp8 copy (and P / part) — returns an empty tensor
-  TORCH_CHECK(write_out || ((epi == HQ_EPI_GELUD || epi == HQ_EPI_DMUL) && out8.has_value() && out8->defined()),
+  TORCH_CHECK(write_out || ((epi == HQ_EPI_GELUD || epi == HQ_EPI_DMUL) && has(out8)),
               "gemm_fp8: write_out=False needs a GELUD / DMUL epilogue with out8");
   Tensor C = write_out ? at::empty({M, N}, A8.options().dtype(BF16)) : at::empty({0}, A8.options().dtype(BF16));
   uint16_t* P = nullptr;
@@ -377,23 +389,23 @@ Tensor gemm_fp8(Tensor A8, Tensor B8, int64_t epi, c10::optional<Tensor> bias, T
   float* pp = nullptr;
   bool code8 = true;
   if (epi == HQ_EPI_DMUL) {
-    TORCH_CHECK(part.has_value() && part->defined(), "gemm_fp8: DMUL needs `part` [M/256, N]");
+    TORCH_CHECK(has(part), "gemm_fp8: DMUL needs `part` [M/256, N]");
     check(*part, F32, "part");
     TORCH_CHECK(part->numel() == (M / 256) * N, "gemm_fp8: part must hold [M/256, N]");
     pp = ptr<float>(*part);
   }
   if (epi == HQ_EPI_RESID) {
-    TORCH_CHECK(resid.has_value() && resid->defined(), "gemm_fp8: RESID needs `resid`");
+    TORCH_CHECK(has(resid), "gemm_fp8: RESID needs `resid`");
     check(*resid, BF16, "resid");
     TORCH_CHECK(resid->size(0) == M && resid->size(1) == N, "gemm_fp8: resid shape");
     P = ptr<uint16_t>(*resid);
   }
   if (epi == HQ_EPI_GELUD || epi == HQ_EPI_DMUL) {
-    TORCH_CHECK(pre.has_value() && pre->defined(), "gemm_fp8: GELUD / DMUL need `pre` (gelu')");
+    TORCH_CHECK(has(pre), "gemm_fp8: GELUD / DMUL need `pre` (gelu')");
     // gelu' travels as the 8-bit code (hq_gd_encode8, a uint8 `pre`) between the fp8 FFN1 forward and the fp8
     // FFN2 dgrad, else as bf16.  The fp8 DMUL reads only the code; the fp8 GELUD writes bf16 gelu' (beside its
     // e4m3 act) only together with the bf16 act, i.e. when the backward will run the FFN2 dgrad in bf16.
-    const bool with8 = out8.has_value() && out8->defined();
+    const bool with8 = has(out8);
     code8 = pre->scalar_type() == at::kByte;
     if (code8) {
       TORCH_CHECK(with8 && pre->is_cuda() && pre->is_contiguous(),
@@ -405,16 +417,14 @@ Tensor gemm_fp8(Tensor A8, Tensor B8, int64_t epi, c10::optional<Tensor> bias, T
     }
     TORCH_CHECK(pre->size(0) == M && pre->size(1) == N, "gemm_fp8: pre shape");
     P = reinterpret_cast<uint16_t*>(pre->data_ptr());
-    if (out8.has_value() && out8->defined()) {
+    if (has(out8)) {
       TORCH_CHECK(out8->scalar_type() == (fwd ? at::kFloat8_e4m3fn : at::kFloat8_e5m2),
                   "gemm_fp8: out8 must be float8_e4m3fn (GELUD) / float8_e5m2 (DMUL)");
       TORCH_CHECK(out8->is_cuda() && out8->element_size() == 1 && out8->is_contiguous() && out8->numel() == M * N,
                   "gemm_fp8: out8 must be a contiguous 1-byte [M,N] tensor");
-      TORCH_CHECK(state.has_value() && state->defined(), "gemm_fp8: out8 needs the delayed-scaling state");
-      check(*state, F32, "state");
-      TORCH_CHECK(state->numel() == 4, "gemm_fp8: state must be f32[4]");
+      TORCH_CHECK(has(state), "gemm_fp8: out8 needs the delayed-scaling state");
       C8 = reinterpret_cast<uint8_t*>(out8->data_ptr());
-      q8 = ptr<float>(*state);
+      q8 = state4(state, "state", "gemm_fp8: state must be f32[4]");
     }
   }
   hq_gemm_fp8(reinterpret_cast<const uint8_t*>(A8.data_ptr()), reinterpret_cast<const uint8_t*>(B8.data_ptr()),
@@ -530,7 +540,7 @@ Tensor gelu_bwd(Tensor dout, Tensor pre, c10::optional<Tensor> g_bias, bool accu
   TORCH_CHECK(dout.sizes() == pre.sizes() && dout.dim() == 2, "shape");
   const int64_t T = dout.size(0), N = dout.size(1);
   TORCH_CHECK(N % 8 == 0, "N must be a multiple of 8");
-  if (g_bias.has_value() && g_bias->defined()) TORCH_CHECK(g_bias->numel() == N, "g_bias shape");
+  if (has(g_bias)) TORCH_CHECK(g_bias->numel() == N, "g_bias shape");
   c10::DeviceGuard g(dout.device());
   auto dpre = at::empty_like(dout);
   auto part = at::empty({hq_rowblock_partials((int)T), N}, dout.options().dtype(F32));
@@ -562,11 +572,8 @@ std::vector<Tensor> attn_fwd(Tensor qkv, Tensor key_bias, int64_t B, int64_t L, 
                              int64_t opid, double scale, c10::optional<Tensor> q8, int64_t phase) {
   check_attn(qkv, key_bias, B, L, nh);
   const int64_t H = qkv.size(1) / 3;
-  const bool want8 = q8.has_value() && q8->defined();
-  if (want8) {
-    check(*q8, F32, "q8");
-    TORCH_CHECK(q8->numel() == 4, "q8 must be the f32[4] delayed-scaling state");
-  }
+  const bool want8 = has(q8);
+  float* q8p = state4(q8, "q8", "q8 must be the f32[4] delayed-scaling state");
   c10::DeviceGuard g(qkv.device());
   auto ctx = at::empty({B * L, H}, qkv.options());
   auto lse = at::empty({B, nh, L}, key_bias.options());
@@ -575,8 +582,8 @@ std::vector<Tensor> attn_fwd(Tensor qkv, Tensor key_bias, int64_t B, int64_t L, 
   Tensor ctx8 = want8 ? at::empty({B * L, H}, qkv.options().dtype(at::kFloat8_e4m3fn)) : Tensor();
   hq_attn_fwd(ptr<uint16_t>(qkv), ptr<float>(key_bias), ptr<uint16_t>(ctx), ptr<float>(lse),
               mbytes ? ptr<uint16_t>(mbits) : nullptr, (int)B, (int)L, (int)nh, 64, (float)p, u32(seed), u32(opid),
-              (float)scale, cur_stream(), want8 ? reinterpret_cast<uint8_t*>(ctx8.data_ptr()) : nullptr,
-              want8 ? ptr<float>(*q8) : nullptr, (int)(phase % 3));
+              (float)scale, cur_stream(), want8 ? reinterpret_cast<uint8_t*>(ctx8.data_ptr()) : nullptr, q8p,
+              (int)(phase % 3));
   if (want8) return {ctx, lse, mbits, ctx8};
   return {ctx, lse, mbits};
 }
@@ -597,22 +604,18 @@ std::vector<Tensor> attn_bwd_impl(Tensor dctx, Tensor qkv, Tensor ctx, Tensor ls
     TORCH_CHECK(mbits.numel() * 2 == (int64_t)hq_attn_mask_bytes((int)B, (int)L, (int)nh), "dropout mask size");
   }
   c10::DeviceGuard g(qkv.device());
-  const bool want8 = q8.has_value() && q8->defined();
+  const bool want8 = has(q8);
   TORCH_CHECK(write_bf16 || want8, "attn_bwd: write_bf16=False needs q8");
   auto dqkv = write_bf16 ? at::empty_like(qkv) : at::empty({0}, qkv.options());
   auto delta = at::empty({B, nh, L}, lse.options());
   Tensor bpart = write_bf16 ? Tensor() : at::empty({B * ((L + 31) / 32), qkv.size(1)}, lse.options());
-  Tensor dqkv8;
-  if (want8) {
-    check(*q8, F32, "q8");
-    TORCH_CHECK(q8->numel() == 4, "attn_bwd: q8 must be f32[4]");
-    dqkv8 = at::empty(qkv.sizes(), qkv.options().dtype(at::kFloat8_e5m2));
-  }
+  float* q8p = state4(q8, "q8", "attn_bwd: q8 must be f32[4]");
+  Tensor dqkv8 = want8 ? at::empty(qkv.sizes(), qkv.options().dtype(at::kFloat8_e5m2)) : Tensor();
   hq_attn_bwd(ptr<uint16_t>(dctx), ptr<uint16_t>(qkv), ptr<uint16_t>(ctx), ptr<float>(lse), ptr<float>(key_bias),
               p > 0 ? ptr<uint16_t>(mbits) : nullptr, write_bf16 ? ptr<uint16_t>(dqkv) : nullptr, ptr<float>(delta), (int)B,
               (int)L, (int)nh, 64, (float)p, (float)scale, deterministic, cur_stream(),
-              want8 ? reinterpret_cast<uint8_t*>(dqkv8.data_ptr()) : nullptr, want8 ? ptr<float>(*q8) : nullptr,
-              (int)(phase % 3), write_bf16 ? nullptr : ptr<float>(bpart));
+              want8 ? reinterpret_cast<uint8_t*>(dqkv8.data_ptr()) : nullptr, q8p, (int)(phase % 3),
+              write_bf16 ? nullptr : ptr<float>(bpart));
   if (!write_bf16) return {dqkv, dqkv8, bpart};
   if (want8) return {dqkv, dqkv8};
   return {dqkv};
@@ -670,7 +673,7 @@ void adamw(Tensor master, c10::optional<Tensor> compute, Tensor grad, Tensor m, 
   check(master, F32, "master"); check_opt(compute, BF16, "compute"); check(grad, F32, "grad");
   check(m, F32, "exp_avg"); check(v, F32, "exp_avg_sq"); check(chunks, I64, "chunks"); check_opt(clip_coef, F32, "clip");
   TORCH_CHECK(grad.numel() == master.numel() && m.numel() == master.numel() && v.numel() == master.numel(), "arena sizes");
-  if (compute.has_value() && compute->defined()) TORCH_CHECK(compute->numel() == master.numel(), "compute size");
+  if (has(compute)) TORCH_CHECK(compute->numel() == master.numel(), "compute size");
   TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 2, "chunks must be [n,2] int64");
   c10::DeviceGuard g(master.device());
   hq_adamw(ptr<float>(master), optr<uint16_t>(compute), ptr<float>(grad), ptr<float>(m), ptr<float>(v),
@@ -686,7 +689,7 @@ void adamod(Tensor master, c10::optional<Tensor> compute, Tensor grad, Tensor m,
   check_opt(clip_coef, F32, "clip");
   TORCH_CHECK(grad.numel() == master.numel() && m.numel() == master.numel() && v.numel() == master.numel() &&
                   n.numel() == master.numel(), "arena sizes");
-  if (compute.has_value() && compute->defined()) TORCH_CHECK(compute->numel() == master.numel(), "compute size");
+  if (has(compute)) TORCH_CHECK(compute->numel() == master.numel(), "compute size");
   TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 2, "chunks must be [n,2] int64");
   c10::DeviceGuard g(master.device());
   hq_adamod(ptr<float>(master), optr<uint16_t>(compute), ptr<float>(grad), ptr<float>(m), ptr<float>(v), ptr<float>(n),
@@ -772,10 +775,10 @@ std::vector<Tensor> qa_loss(Tensor logits, Tensor cls, Tensor reg, Tensor t_star
   TORCH_CHECK(NL >= 1 && NL <= 8 && reg.numel() == 2 * B, "cls [B, NL<=8], reg [B, 2]");
   TORCH_CHECK(t_start.numel() == B && t_end.numel() == B && t_cls.numel() == B && t_rs.numel() == B &&
                   t_re.numel() == B, "targets must have B elements");
-  TORCH_CHECK(!lw.has_value() || !lw->defined() || lw->numel() == NL, "label weights [NL]");
+  TORCH_CHECK(!has(lw) || lw->numel() == NL, "label weights [NL]");
   TORCH_CHECK(weights.size() == 5 && kind >= 0 && kind <= 2, "loss config");
   int nseg = 1;
-  if (seg_len.has_value() && seg_len->defined()) {   // exact-objective merge: one segment per micro-batch
+  if (has(seg_len)) {   // exact-objective merge: one segment per micro-batch
     check(*seg_len, at::kInt, "segment lengths");
     nseg = (int)seg_len->numel();
     TORCH_CHECK(nseg >= 1 && B % nseg == 0, "segments must split the batch into equal parts");
@@ -794,7 +797,7 @@ std::vector<Tensor> qa_loss(Tensor logits, Tensor cls, Tensor reg, Tensor t_star
   hq_qa_loss(ptr<float>(logits), ptr<float>(cls), ptr<float>(reg), ptr<int64_t>(t_start), ptr<int64_t>(t_end),
              ptr<int64_t>(t_cls), ptr<float>(t_rs), ptr<float>(t_re), optr<float>(lw), ptr<float>(dlog), ptr<float>(dheads),
              ptr<float>(losses), ptr<float>(part), ticket(logits, 1), (int)B, (int)(T / B), (int)NL, cfg,
-             nseg > 1 || (seg_len.has_value() && seg_len->defined()) ? optr<int>(seg_len) : nullptr, nseg, cur_stream());
+             nseg > 1 || has(seg_len) ? optr<int>(seg_len) : nullptr, nseg, cur_stream());
   return {losses, dlog, dheads};
 }
 
@@ -809,7 +812,7 @@ Tensor qa_heads_bwd(Tensor seq, int64_t L, Tensor dlog, Tensor dheads, c10::opti
   check_opt(gscale, F32, "gscale");
   TORCH_CHECK(dlog.numel() == 2 * T && dheads.numel() == 16 * B && pooled.numel() == B * H && reg.numel() == 2 * B,
               "qa_heads_bwd: operand shapes");
-  TORCH_CHECK(!gscale.has_value() || !gscale->defined() || gscale->numel() == 1, "gscale is a scalar");
+  TORCH_CHECK(!has(gscale) || gscale->numel() == 1, "gscale is a scalar");
   const HqHeadWeights hw = head_weights(w, H, NL);
   const HqHeadWeights hg = head_weights(grads, H, NL);  // same shapes / dtype checks for the gradients
   HqHeadGrads gg{const_cast<float*>(hg.wp), const_cast<float*>(hg.bp), const_cast<float*>(hg.wc),
@@ -869,17 +872,12 @@ void f32_embed_bwd(Tensor dy, Tensor ids, Tensor pids, Tensor tids, Tensor ww, T
   auto part = at::empty({hq_f32_part_rows((int)T), 4 * H}, dy.options());
   // deterministic: per-call scratch of the sorted-run path (sort pairs, digit histograms of the widest key, carry
   // rows), shared by the word, position and type passes
-  Tensor pairs, sort_tmp, carry;
-  HqEmbScratch sc{};
+  EmbScratch es;
   if (deterministic) {
     const int V = (int)ww.size(0), P = (int)wp.size(0);
     size_t sort_bytes = std::max(hq_sort_ids_bytes((int)T, V), hq_sort_ids_bytes((int)T, P));
     if (n_types > 2) sort_bytes = std::max(sort_bytes, hq_sort_ids_bytes((int)T, n_types));
-    pairs = at::empty({4, T}, ids.options().dtype(at::kInt));
-    sort_tmp = at::empty({(int64_t)std::max<size_t>(sort_bytes, 1)}, ids.options().dtype(at::kByte));
-    carry = at::empty({(int64_t)std::max(hq_f32_embed_run_chunks((int)T), 1) * 2, H}, dy.options());
-    int32_t* pr = pairs.data_ptr<int32_t>();
-    sc = HqEmbScratch{pr, pr + T, pr + 2 * T, pr + 3 * T, sort_tmp.data_ptr(), sort_bytes, ptr<float>(carry), nullptr};
+    es = emb_scratch(ids, dy.options(), T, H, sort_bytes, std::max(hq_f32_embed_run_chunks((int)T), 1), nullptr);
   }
   float* t0 = ptr<float>(g_type);
   hq_f32_embed_bwd(ptr<float>(dy), ptr<int64_t>(ids), ptr<int64_t>(pids), ptr<int64_t>(tids), ptr<float>(ww), ptr<float>(wp),
@@ -887,7 +885,7 @@ void f32_embed_bwd(Tensor dy, Tensor ids, Tensor pids, Tensor tids, Tensor ww, T
                    ptr<float>(g_pos), t0, ptr<float>(part),
                    outs4(ptr<float>(g_gamma), ptr<float>(g_beta), n_types <= 2 ? t0 : nullptr, n_types == 2 ? t0 + H : nullptr),
                    (int)T, (int)H, (int)pad_word, (int)pad_pos, (float)p, u32(seed), u32(opid), accumulate,
-                   (int)ww.size(0), (int)wp.size(0), (int)wt.size(0), s, deterministic ? &sc : nullptr);
+                   (int)ww.size(0), (int)wp.size(0), (int)wt.size(0), s, deterministic ? &es.sc : nullptr);
 }
 
 std::vector<Tensor> f32_ln_fwd(Tensor a, Tensor resid, Tensor gamma, Tensor beta, double eps, double p, int64_t seed,
@@ -908,8 +906,8 @@ std::vector<Tensor> f32_ln_bwd(Tensor dy, c10::optional<Tensor> dy2, Tensor z, T
                                c10::optional<Tensor> g_beta, c10::optional<Tensor> g_bias, bool accumulate,
                                c10::optional<Tensor> beta) {
   f32_rows(dy, "dy"); f32_rows(z, "z"); f32_rows(gamma, "gamma"); f32_rows(mean, "mean"); f32_rows(rstd, "rstd");
-  if (dy2.has_value() && dy2->defined()) { f32_rows(*dy2, "dy2"); TORCH_CHECK(dy2->sizes() == dy.sizes(), "dy2 shape"); }
-  if (beta.has_value() && beta->defined()) f32_rows(*beta, "beta");
+  if (has(dy2)) { f32_rows(*dy2, "dy2"); TORCH_CHECK(dy2->sizes() == dy.sizes(), "dy2 shape"); }
+  if (has(beta)) f32_rows(*beta, "beta");
   TORCH_CHECK(dy.sizes() == z.sizes() && gamma.numel() == dy.size(1), "ln_bwd shapes");
   c10::DeviceGuard g(dy.device());
   const int64_t T = dy.size(0), H = dy.size(1);
@@ -1093,7 +1091,7 @@ PYBIND11_MODULE(_hq_kernels, m) {
   m.def("span_fwd", &span_fwd);
   m.def("span_bwd", &span_bwd);
   m.def("set_dropout_seed", [](c10::optional<Tensor> t) {
-    if (t.has_value() && t->defined()) {
+    if (has(t)) {
       TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->numel() >= 1, "seed must be a GPU int32 tensor");
       hq_set_dropout_seed_ptr(reinterpret_cast<const uint32_t*>(t->data_ptr()));
     } else {

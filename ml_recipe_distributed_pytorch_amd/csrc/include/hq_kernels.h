@@ -13,22 +13,34 @@ constexpr float kHqGdLo = -0.12890625f;
 constexpr float kHqGdStep = 1.2578125f / 255.f;
 constexpr float kHqGdInv = 255.f / 1.2578125f;       // encode: q = rne(fma(g, kHqGdInv, kHqGdOff)), clamp 0…255
 constexpr float kHqGdOff = -kHqGdLo * kHqGdInv;
-void hq_gelud_encode8(const uint16_t* g, uint8_t* q, size_t n, hipStream_t s);   // bf16 gelu' -> code (n % 8 == 0)
 
 struct HqOuts {  // up to 4 fp32 column-sum destinations (null = skip), passed by value
   float* p[4];
 };
 
-// ---- dropout streams ---------------------------------------------------------------------------
+// ---- rowops.hip: process-wide state, element-wise ops, column sums ------------------------------------------------
 // Register (or clear with nullptr) a device uint32 seed that every dropout kernel launched afterwards reads
-// instead of its host seed argument (norm.hip).
+// instead of its host seed argument.
 void hq_set_dropout_seed_ptr(const uint32_t* p);
 struct HqDropKey;
 HqDropKey hq_drop_key(uint32_t seed, uint32_t opid);
+// CU count, queried once per process on the device current at the first call (256 if the query fails)
+int hq_num_cus();
+int hq_rowblock_partials(int T);
+void hq_gelu_fwd(const uint16_t* pre, uint16_t* out, size_t n, hipStream_t s);
+void hq_gelu_bwd(const uint16_t* dout, const uint16_t* pre, uint16_t* dpre, float* part, HqOuts outs, int T, int N,
+                 bool accumulate, hipStream_t s);
+void hq_bias_grad(const uint16_t* dy, float* part, HqOuts outs, int T, int N, bool accumulate, hipStream_t s);
+// out[c] (+)= sum_p part[p][c], part f32 [P][N]
+void hq_colsum(const float* part, int P, int N, float* out, bool accumulate, hipStream_t s);
+// out_q[c] (+)= Σ_p part[p][q·Hq + c] for the (≤ 4) destinations of outs, part f32 [P][N]
+void hq_colsum_outs(const float* part, int P, int N, HqOuts outs, int Hq, bool accumulate, hipStream_t s);
+void hq_zero_f32(float* p, size_t n, hipStream_t s);   // own zero-fill kernel (no runtime memset node in graphs)
+void hq_key_bias(const uint8_t* mask, float* kb, int n, hipStream_t s);
 
 // ---- norm.hip --------------------------------------------------------------------------------
+int hq_ln_rows_per_wave(int T);   // rows a wave of the LayerNorm backward walks at T rows
 int hq_ln_bwd_partials(int T);
-int hq_rowblock_partials(int T);
 // y8 != null (fp8 path): y also as e4m3 under the delayed-scaling state q8 [4] at `phase` (see hq_common.h);
 // resid == null (bf16 only): `a` already is z (an EPI_BDR GEMM wrote it) — only y, mean, rstd are written
 void hq_ln_fwd(const uint16_t* a, const uint16_t* resid, const float* gamma, const float* beta, uint16_t* y, uint16_t* z,
@@ -39,10 +51,19 @@ void hq_ln_bwd(const uint16_t* dy, const uint16_t* dy2, const uint16_t* z, const
                const float* rstd, uint16_t* dz, uint16_t* da, float* part, HqOuts outs, int T, int H, float p,
                uint32_t seed, uint32_t opid, bool accumulate, hipStream_t s, uint8_t* da8 = nullptr,
                float* q8 = nullptr, int phase = 0, const float* beta = nullptr);   // beta: z is the output y
+void hq_ln_guard(const float* master, const int64_t* goff, const int64_t* boff, int n, int H, float ratio, uint8_t* flags,
+                 hipStream_t s);
+
+// ---- sort.hip ----------------------------------------------------------------------------------
+size_t hq_sort_ids_bytes(int T, int V);
+void hq_sort_ids(const int64_t* ids, int T, int V, int32_t* keys, int32_t* rows, int32_t* skeys, int32_t* srows,
+                 void* hist, size_t hist_bytes, hipStream_t s);
+
+// ---- embed.hip ---------------------------------------------------------------------------------
 void hq_embed_fwd(const int64_t* ids, const int64_t* pids, const int64_t* tids, const uint16_t* ww, const uint16_t* wp,
                   const uint16_t* wt, const float* gamma, const float* beta, uint16_t* y, float* mean, float* rstd, int T,
                   int H, float eps, float p, uint32_t seed, uint32_t opid, int V, int P, int NTY, hipStream_t s);
-// deterministic embedding backward scratch (norm.hip: id sort, word-run carries, position partials)
+// deterministic embedding backward scratch (id sort, word-run carries, position partials)
 struct HqEmbScratch {
   int32_t *keys, *rows, *skeys, *srows;   // [T] each: (id, row) pairs and their id-sorted copies
   void* sort_tmp;                          // radix-sort digit histograms (sort_bytes)
@@ -55,10 +76,7 @@ struct HqEmbScratchSizes {
   int chunks, pos_rows;
 };
 HqEmbScratchSizes hq_embed_bwd_scratch(int T, int V, int L, int P);
-size_t hq_sort_ids_bytes(int T, int V);
-void hq_sort_ids(const int64_t* ids, int T, int V, int32_t* keys, int32_t* rows, int32_t* skeys, int32_t* srows,
-                 void* hist, size_t hist_bytes, hipStream_t s);
-// sorted rows per wave of the sorted-run kernels (norm.hip embed_word_kernel, f32_ops.hip f32_embed_run_kernel): the
+// sorted rows per wave of the sorted-run kernels (embed_word_kernel here, f32_ops.hip f32_embed_run_kernel): the
 // unit of their documented summation order
 constexpr int kHqEmbRunChunk = 16;
 // det_pos: every position gradient from a sort of pids + the sorted-run kernels (no position partials, no position
@@ -71,8 +89,6 @@ void hq_embed_bwd(const uint16_t* dy, const int64_t* ids, const int64_t* pids, c
                   int L, const HqEmbScratch& sc, hipStream_t s, bool det_pos = false, bool det_type = false);
 // partial-sum rows embed_bwd needs for T tokens laid out as [T / L][L] (L <= 0: one sequence)
 int hq_embed_bwd_partials(int T, int L);
-void hq_gelu_fwd(const uint16_t* pre, uint16_t* out, size_t n, hipStream_t s);
-void hq_key_bias(const uint8_t* mask, float* kb, int n, hipStream_t s);
 
 // ---- f32_ops.hip: --precision fp32 row-wise ops and flash attention ----------------------------------------------
 int hq_f32_row_partials(int T);   // partial rows of the column-partial kernels for T rows
@@ -103,11 +119,6 @@ void hq_f32_attn_fwd(const float* qkv, const float* key_bias, float* ctx, float*
 void hq_f32_attn_bwd(const float* dctx, const float* qkv, const float* ctx, const float* lse, const float* key_bias,
                      float* dqkv, float* delta, int B, int L, int nh, float p, uint32_t seed, uint32_t opid, float scale,
                      hipStream_t s);
-void hq_ln_guard(const float* master, const int64_t* goff, const int64_t* boff, int n, int H, float ratio, uint8_t* flags,
-                 hipStream_t s);
-void hq_gelu_bwd(const uint16_t* dout, const uint16_t* pre, uint16_t* dpre, float* part, HqOuts outs, int T, int N,
-                 bool accumulate, hipStream_t s);
-void hq_bias_grad(const uint16_t* dy, float* part, HqOuts outs, int T, int N, bool accumulate, hipStream_t s);
 
 // ---- attention.hip ----------------------------------------------------------------------------
 void hq_attn_set_force_slow(int v);          // tests: every ring-forward workgroup takes the slow path
@@ -168,7 +179,6 @@ int hq_gemm_nt_part_rows(int M, int N, int K);
 // 0 = auto (128² tiles for M % 256 != 0 or < 80 % CU fill; else the persistent v3 kernel for K <= 2304,
 // v2 above), 1 = v1, 2 = v2, 3 = v3 (the 256-row kernels wherever M % 256 == 0), 4 = 128² tiles always
 void hq_gemm_set_variant(int v);
-void hq_zero_f32(float* p, size_t n, hipStream_t s);   // own zero-fill kernel (no runtime memset node in graphs)
 void hq_gemm_set_store_policy(int v);   // persistent-kernel epilogue stores: 0 default, 1 nt|sc1 at K <= 768, 2 always
 void hq_gemm_set_stagger(int v);   // v3 start offset of half the workgroups (units of s_sleep(127))
 // v3 tile scheduling: 1 = dynamic (a workgroup's third and later tiles come from per-XCD atomic ticket
@@ -191,7 +201,8 @@ void hq_gemm_nt(const uint16_t* A, const uint16_t* B, uint16_t* C, const float* 
                 float* part, int M, int N, int K, int lda, int ldb, int ldc, int epi, int bn, hipStream_t s,
                 float drop_p = 0.f, uint32_t drop_seed = 0, uint32_t drop_opid = 0, float* ws = nullptr);
 
-// Exact-fp32 strided GEMM on the f32 MFMA (gemm_f32.hip, --precision fp32): C = alpha·A·Bᵀ (+bias[j]) (+R),
+// ------------------------------------------------------------------ gemm_f32.hip
+// Exact-fp32 strided GEMM on the f32 MFMA (--precision fp32): C = alpha·A·Bᵀ (+bias[j]) (+R),
 // A(i,k) = A[i·sa_i + k·sa_k], B(j,k) = B[j·sb_j + k·sb_k] (sa_k == 1 or sa_i == 1; likewise B), batch z =
 // outer·nb_in + inner with per-operand strides (C and R share C's); ksplit > 1 (batch 1): ws holds ksplit M·N slabs.
 int hq_gemm_f32_splits(int M, int N, int K, int batch);
@@ -206,7 +217,8 @@ void hq_gemm_f32x3(const float* A, const float* B, float* C, const float* bias, 
                    int nb_in, long long ba_out, long long ba_in, long long bb_out, long long bb_in, long long bc_out,
                    long long bc_in, float alpha, int ksplit, hipStream_t s);
 
-// Weight-gradient GEMM (gemm_tn.hip): out[N,K] (+)= Aᵀ·B, A = dy [T,N] bf16, B = x [T,K] bf16 (token-major),
+// ------------------------------------------------------------------ gemm_tn.hip
+// Weight-gradient GEMM: out[N,K] (+)= Aᵀ·B, A = dy [T,N] bf16, B = x [T,K] bf16 (token-major),
 // split-K over T into S fp32 slabs part[S][N][K] (caller-provided) reduced into out; with bout != null
 // also the fused bias gradient bout[N] (+)= Σ_t A[t, n] through slabs bpart[S][N].
 // hq_gemm_tn_splits: the split count for this shape, 0 = unsupported (need N%256, K%256 == 0, T >= 128;
@@ -221,7 +233,8 @@ int hq_gemm_tn8_splits(int T, int N, int K);
 void hq_gemm_tn8(const uint8_t* A, const uint8_t* B, const float* sa, const float* sb, float* part, float* out, int T,
                  int N, int K, int S, bool accumulate, hipStream_t s);
 
-// fp8 NT GEMM (gemm_fp8.hip): C = A8·B8ᵀ·sa·sb (+ epilogue), B8 e4m3.  Forward epi ∈ {HQ_EPI_BIAS,
+// ------------------------------------------------------------------ gemm_fp8.hip
+// fp8 NT GEMM: C = A8·B8ᵀ·sa·sb (+ epilogue), B8 e4m3.  Forward epi ∈ {HQ_EPI_BIAS,
 // HQ_EPI_GELUD} with A8 e4m3; backward epi ∈ {HQ_EPI_NONE, HQ_EPI_RESID (C + P), HQ_EPI_DMUL (C ⊙ P,
 // column sums into part[M/256][N])} with A8 e5m2.  C8 != null (GELUD / DMUL): the output also as e4m3 / e5m2 under
 // delayed scaling driven by the 4-float state q8 / phase.
@@ -230,7 +243,12 @@ void hq_gemm_fp8_set_variant(int v);   // 0 auto (persistent but the Q8 DMUL), 2
 void hq_gemm_fp8(const uint8_t* A, const uint8_t* B, uint16_t* C, const float* bias, uint16_t* P, const float* sa,
                  const float* sb, uint8_t* C8, float* q8, int phase, int M, int N, int K, int epi, hipStream_t s,
                  float* part = nullptr, int gd8 = 1);
-// delayed-scaling e4m3 quantiser (one pass): y = x / s(prev amax), amax tracked in q8 (see gemm_fp8.hip)
+
+// ------------------------------------------------------------------ fp8 quantisation (fp8.hip); n % 8 == 0
+void hq_gelud_encode8(const uint16_t* g, uint8_t* q, size_t n, hipStream_t s);   // bf16 gelu' -> code (n % 8 == 0)
+void hq_amax_bf16(const uint16_t* x, size_t n, unsigned* amax, hipStream_t s);
+void hq_fp8_quant(const uint16_t* x, uint8_t* y, size_t n, const unsigned* amax, float* scale, hipStream_t s);
+// delayed-scaling e4m3 quantiser (one pass): y = x / s(prev amax), amax tracked in q8 (see hq_common.h)
 void hq_fp8_quant_delayed(const uint16_t* x, uint8_t* y, size_t n, float* q8, int phase, hipStream_t s);
 long long hq_fp8_quant_multi_blocks(long long n8);   // blocks of one segment of n8 8-element groups
 // fp8 producers write per-wave amax partials into this device scratch (>= n floats, current device) and
@@ -247,25 +265,17 @@ int hq_fp8_fold_pending();
 void hq_fp8_quant_delayed_multi(const uint16_t* x, uint8_t* y, const long long* seg, int nseg, long long blocks,
                                 float* states, int phase, hipStream_t s);
 
+// ------------------------------------------------------------------ transpose.hip
 // tiles: int32 [ntiles][6] = (src_off, dst_off, rows, cols, r0, c0); src [rows][cols] -> dst [cols][rows]
 void hq_transpose_tiles(const uint16_t* src, uint16_t* dst, const int* tiles, int ntiles, hipStream_t s);
 void hq_transpose_tiles8(const uint8_t* src, uint8_t* dst, const int* tiles, int ntiles, hipStream_t s);
-// out[c] (+)= sum_p part[p][c], part f32 [P][N]
-void hq_colsum(const float* part, int P, int N, float* out, bool accumulate, hipStream_t s);
 
-// ------------------------------------------------------------------ fp8 (fp8.hip); n % 8 == 0
-void hq_amax_bf16(const uint16_t* x, size_t n, unsigned* amax, hipStream_t s);
-void hq_fp8_quant(const uint16_t* x, uint8_t* y, size_t n, const unsigned* amax, float* scale, hipStream_t s);
-
-// ------------------------------------------------------------------ QA span head (norm.hip)
+// ------------------------------------------------------------------ QA heads (heads.hip): the span head alone ...
 void hq_span_fwd(const uint16_t* seq, const float* w, const float* b, float* logits, int T, int H, hipStream_t s);
 // part: [hq_ln_bwd_partials(T)][2][H] scratch; dw: [2][H] (+)=
 void hq_span_bwd(const uint16_t* seq, const float* w, const float* g, uint16_t* dseq, float* part, float* dw, int T,
                  int H, bool accumulate, hipStream_t s);
-// out_q[c] (+)= Σ_p part[p][q·Hq + c] for the (≤ 4) destinations of outs, part f32 [P][N]
-void hq_colsum_outs(const float* part, int P, int N, HqOuts outs, int Hq, bool accumulate, hipStream_t s);
-
-// ------------------------------------------------------------------ fused QA heads + losses (heads.hip)
+// ... and the fused QA heads + losses
 struct HqHeadWeights {  // fp32 master weights: pooler, classifier [NL,H], reg start/end [1,H], span [2,H]
   const float *wp, *bp, *wc, *bc, *wrs, *brs, *wre, *bre, *wsp, *bsp;
 };

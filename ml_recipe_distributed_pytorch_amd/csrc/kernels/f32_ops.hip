@@ -151,20 +151,9 @@ __global__ __launch_bounds__(256) void f32_embed_bwd_kernel(const float* __restr
 }
 
 // ---- deterministic table gradients: sorted runs instead of atomics (hq_f32_embed_bwd with deterministic = true)
-// One pair of kernels serves the word, position and type tables; KEY picks which id of a token is the key
-// (0: ids, 1: pids, 2: tids).  The tokens are sorted by key with the stable hq_sort_ids, so the tokens of one key
-// (its "run") are contiguous in the sorted list and stay in token order.  The summation order of a table row is:
-//   * the sorted list is cut into chunks of kRunCH consecutive sorted positions, chunk c = [c·kRunCH, (c+1)·kRunCH),
-//     one wave per chunk; the rows of ONE key inside ONE chunk form a piece;
-//   * a piece is summed from zero in token order: piece = ((0 + dx[t0]) + dx[t1]) + …, every dx recomputed by the
-//     wave exactly as f32_embed_bwd_kernel computes it;
-//   * a run that lies inside one chunk is one piece; a run that crosses chunk boundaries has one piece per chunk
-//     it touches, and the pieces are added in chunk order onto the first: total = ((piece_c + piece_c+1) + …);
-//   * accumulate adds the existing table row last: row = total + row; fresh stores row = total;
-//   * the skipped key (the padding id / padding position) gets no gradient, a key that never occurs keeps its row.
-// Pieces of crossing runs travel through the carry buffer [chunks][2][H]: slot 0 of chunk c holds the chunk's first
-// piece when its run began in an earlier chunk, slot 1 the chunk's last piece when its run began in this chunk and
-// continues into the next; f32_embed_carry_kernel, run by the chunk that holds slot 1, completes the row.
+// The fp32 pair of the sorted-run kernels: chunks, pieces, carries and the summation order of a table row are
+// stated once, above embed_word_kernel in embed.hip.  Specific to this pair: every dx is recomputed exactly as
+// f32_embed_bwd_kernel computes it, and lane owns the columns q·64 + lane (any H, no H % 4 requirement).
 constexpr int kRunCH = kHqEmbRunChunk;   // sorted rows per wave (<= 64: one row's metadata per lane)
 
 template <int NC, int KEY>

@@ -1469,16 +1469,6 @@ unsigned* nt3_sched_slot(hipStream_t s) {
   return p->base + kSchedWords * (p->streams.size() - 1);
 }
 
-int nts_num_cus() {
-  static int ncu = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
-  return ncu;
-}
-
 // vS split-K factor: only epilogues without column partials / GELU, grids below half a workgroup per CU,
 // and at least 8 K-tiles per split; HQ_GEMM_SPLITK=0 disables (A/B), N > 1 forces up to N.
 int g_nts_splitk = [] {
@@ -1488,7 +1478,7 @@ int g_nts_splitk = [] {
 template <int EPI>
 int nts_ksplit(int tiles, int nk) {
   if (!(EPI == HQ_EPI_NONE || EPI == HQ_EPI_BIAS || EPI == HQ_EPI_RESID) || g_nts_splitk == 0) return 1;
-  int ks = g_nts_splitk > 1 ? g_nts_splitk : (2 * tiles <= nts_num_cus() ? 2 * nts_num_cus() / tiles : 1);
+  int ks = g_nts_splitk > 1 ? g_nts_splitk : (2 * tiles <= hq_num_cus() ? 2 * hq_num_cus() / tiles : 1);
   ks = std::min(ks, std::min(4, nk / 8));
   return ks > 1 ? ks : 1;
 }
@@ -1532,22 +1522,20 @@ void launch_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const float* 
   // K = 768 / 2304 on the b256 shapes, -1-3 % at K = 3072: tools/gemm_nt3_check.py, profiles/s3_gemm_v3)
   // (and at any K when the half-tile tail applies: at K = 3072 v3 + tail beat v2 + tail by 0.2-2.8 % on two
   // boxes, profiles/r3_halftail)
-  const int ncu_t = nts_num_cus(), rt_t = grid % ncu_t;
+  const int ncu_t = hq_num_cus(), rt_t = grid % ncu_t;
   const bool tail_t = (g_gemm_stagger & kHalfTail) && EPI != HQ_EPI_DGELU && EPI != HQ_EPI_DMUL && rt_t > 0 &&
                       2 * rt_t <= ncu_t && grid > ncu_t;
   const bool v3_auto = g_gemm_variant == 0 && (K <= 2304 || tail_t);
   if (bn == 256 && (g_gemm_variant == 3 || v3_auto) && K >= 2 * BK && srd_ok) {
     constexpr size_t lds = 2 * 2 * 256 * 128 + 64 * 144 + 2 * 256 * 4 + 16 + 1024 + 3 * 32 * 144;
-    static int ncu = [] {
-      int dev = 0, n = 0;
-      (void)hipGetDevice(&dev);
-      (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    static bool init = [] {
       for (const void* f : {(const void*)gemm_nt3_kernel<EPI, false, false>, (const void*)gemm_nt3_kernel<EPI, true, false>,
                             (const void*)gemm_nt3_kernel<EPI, false, true>, (const void*)gemm_nt3_kernel<EPI, true, true>})
         (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      return n > 0 ? n : 256;
+      return true;
     }();
-    const int nwg = std::min(grid, ncu);
+    (void)init;
+    const int nwg = std::min(grid, ncu_t);
     unsigned* sched = (g_gemm_sched && grid > 2 * nwg) ? nt3_sched_slot(s) : nullptr;
     // streamed (nt | sc1) epilogue stores: epilogues without an operand load, K <= 768 (g_store_policy 1), or at any K
     // (2, A/B only), or never (0)
@@ -1578,7 +1566,7 @@ void launch_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const float* 
                          lda, ldb, ldc, dr);
     } else {
       // half-tile tail: rt more blocks, the last 2·rt of them halves of the last rt tiles
-      const int ncu = nts_num_cus(), rt = grid % ncu;
+      const int ncu = hq_num_cus(), rt = grid % ncu;
       const bool ht = (g_gemm_stagger & kHalfTail) && EPI != HQ_EPI_DGELU && EPI != HQ_EPI_DMUL && rt > 0 &&
                       2 * rt <= ncu && grid > ncu;
       hipLaunchKernelGGL((gemm_nt2_kernel<EPI, 8>), dim3(ht ? grid + rt : grid), dim3(kThreads), lds, s, A, B, C, bias, P,
@@ -1627,12 +1615,7 @@ int hq_gemm_nt_supported(int M, int N, int K) {
   const int big = (M % BM == 0) ? (N % 256 == 0 ? 256 : 128) : 0;
   if (g_gemm_variant == 4 || !big) return 1;
   if (g_gemm_variant != 0) return big;
-  static int ncu = [] {
-    int dev = 0, n = 0;
-    (void)hipGetDevice(&dev);
-    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-    return n > 0 ? n : 256;
-  }();
+  const int ncu = hq_num_cus();
   const long tiles = (long)(M / BM) * (N / big);
   const long waves = (tiles + ncu - 1) / ncu;
   return tiles * 5 >= waves * ncu * 4 ? big : 1;

@@ -726,7 +726,7 @@ class BertForQuestionAnswering(nn.Module):
         if attention_mask is None:
             key_bias = torch.zeros(B, L, dtype=torch.float32, device=dev)
         elif dev.type == "cuda" and attention_mask.dtype in (torch.bool, torch.uint8):
-            from .._native import kernels   # one own kernel (norm.hip key_bias_kernel)
+            from .._native import kernels   # one own kernel (rowops.hip key_bias_kernel)
             key_bias = kernels().key_bias(attention_mask.to(dev).contiguous())
         else:
             key_bias = (1.0 - attention_mask.to(dev, torch.float32)) * -10000.0

@@ -167,7 +167,7 @@ class ParamStore:
         return self._fp8[key]
 
     def _requantize_fp8(self):
-        """Every registered weight -> e4m3 in ONE launch (gemm_fp8.hip quant_delayed_multi_kernel), each
+        """Every registered weight -> e4m3 in ONE launch (fp8.hip quant_delayed_multi_kernel), each
         under its own delayed-scaling state (the amax of the previous update sets the scale); the first
         call seeds every state by current scaling.  Replaces one launch per weight (48 × ~13 µs)."""
         from .. import ops

@@ -249,7 +249,7 @@ def linear_fwd_fp8(x, w8s, b):
 
 class Fp8DelayedState:
     """Per-site delayed-scaling state of an fp8 GEMM input: a device f32[4] (three rotating amax slots
-    + the scale in use, see gemm_fp8.hip) and a host step counter selecting the slots — so neither the
+    + the scale in use, see hq_common.h and fp8.hip) and a host step counter selecting the slots — so neither the
     quantiser nor the GEMM ever synchronises with the host.  Forward inputs are e4m3 (scale = 2·amax/448);
     backward activation gradients are e5m2 (scale = 64·amax/57344, ``grad=True``; hq_common.h margins)."""
 

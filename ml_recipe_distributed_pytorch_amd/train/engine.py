@@ -384,7 +384,7 @@ class TrainEngine:
         if self.reducer is not None:
             self.reducer.prepare(sync=boundary or not self.no_sync_accum)
         defer = self._fp8_defer_folds()
-        if defer:   # the fp8 sites' amax folds run batched at the end of the micro-step (gemm_fp8.hip, FoldDefer)
+        if defer:   # the fp8 sites' amax folds run batched at the end of the micro-step (fp8.hip, FoldDefer)
             kernels().fp8_fold_defer(True)
         try:
             preds = self.model(**inputs)

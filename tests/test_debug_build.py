@@ -19,13 +19,15 @@ HIPCC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not available")
 def test_debug_kernels_compile(tmp_path):
-    src = os.path.join(CSRC, "kernels", "norm.hip")
-    out = tmp_path / "norm_debug.o"
-    r = subprocess.run([HIPCC, "-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950", "-DHQ_DEBUG=1",
-                        "-I" + os.path.join(CSRC, "include"), "-c", src, "-o", str(out)],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout
-    assert out.stat().st_size > 0
+    # the row-wise kernel files: LayerNorm, the embedding (id and partial-row assertions), its sort, the column sums
+    for name in ("norm", "embed", "sort", "rowops"):
+        src = os.path.join(CSRC, "kernels", name + ".hip")
+        out = tmp_path / (name + "_debug.o")
+        r = subprocess.run([HIPCC, "-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950", "-DHQ_DEBUG=1",
+                            "-I" + os.path.join(CSRC, "include"), "-c", src, "-o", str(out)],
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout
+        assert out.stat().st_size > 0
 
 
 def test_debug_proxy_syncs_and_names_op(monkeypatch):

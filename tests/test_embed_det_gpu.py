@@ -1,8 +1,8 @@
 """The atomic-free embedding backward behind ``ops.deterministic()``: the fp32 kernels' sorted-run path for the word,
 position and (> 2 types) type tables, and the bf16 kernels' deterministic-positions / sorted-type modes.
 
-Every table row is summed in a documented order (f32_ops.hip f32_embed_run_kernel, norm.hip embed_word_kernel):
-tokens sorted stably by the table's key, the sorted list cut into chunks of ``embed_run_chunk()`` positions; the rows
+Every table row is summed in a documented order (stated above embed.hip embed_word_kernel; the fp32 pair of kernels
+is f32_ops.hip f32_embed_run_kernel): tokens sorted stably by the table's key, the sorted list cut into chunks of ``embed_run_chunk()`` positions; the rows
 of one key inside one chunk (a piece) are summed from zero in token order, the pieces of a run that crosses chunks are
 added in chunk order, and accumulate adds the existing row last.  The tests check that order bit for bit, the values
 against the fp32 oracle, run-to-run equality, and whole training steps."""

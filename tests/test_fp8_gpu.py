@@ -1,4 +1,4 @@
-"""Own fp8 (OCP e4m3) NT GEMM on the block-scaled MFMA (gemm_fp8.hip) and the delayed-scaling quantiser,
+"""Own fp8 (OCP e4m3) NT GEMM on the block-scaled MFMA (gemm_fp8.hip) and the delayed-scaling quantiser (fp8.hip),
 vs fp32 torch references of the dequantised operands."""
 import pytest
 import torch
@@ -557,7 +557,7 @@ def test_gemm_fp8_persistent_matches_per_tile(cuda, epi, q8):
 @pytest.mark.gpu
 def test_fp8_deferred_amax_folds_match_immediate(cuda):
     """TrainEngine under --precision fp8 with the sites' amax folds batched at the end of each micro-step
-    (gemm_fp8.hip FoldDefer; producers publish their dequant scale themselves) against one fold launch per site:
+    (fp8.hip FoldDefer; producers publish their dequant scale themselves) against one fold launch per site:
     bitwise the same losses, weights and delayed-scaling states over steps that cross calibration, with a 2-way
     accumulation (every state produced twice per optimizer step) and nothing left pending afterwards."""
     from types import SimpleNamespace

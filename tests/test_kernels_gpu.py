@@ -165,7 +165,7 @@ def test_embedding(cuda, H, ntypes, p, layout):
 
 @pytest.mark.parametrize("V,T", [(200, 1000), (30522, 98304 + 17), (30522, 1), (70000, 5000), (1000, 4096)])
 def test_sort_ids_is_a_stable_sort(cuda, V, T):
-    """The embedding backward's own LSD radix sort (norm.hip sort_*_kernel, 1 / 2 / 3 passes of 8 bits) equals a
+    """The embedding backward's own LSD radix sort (sort.hip sort_*_kernel, 1 / 2 / 3 passes of 8 bits) equals a
     stable sort: ids ascending, rows of one id in token order — and the same permutation every run."""
     k = _native.kernels()
     g = torch.Generator().manual_seed(V + T)

@@ -8,7 +8,7 @@ weight-gradient GEMMs on a side stream (``HQ_WGRAD_STREAM=1``) the comm-stream c
 all-reduce reads each bucket must equal the final gradients (stream-ordering test).
 
 One optimizer step without clipping, so every element is independent: the word / position embedding
-gradients are scattered with float atomics (norm.hip embed_bwd, order-nondeterministic), which would
+gradients are scattered with float atomics (embed.hip embed_bwd, order-nondeterministic), which would
 otherwise leak through the global grad norm into every parameter.  Those two tensors are compared with a
 tolerance, everything else bitwise."""
 import pytest

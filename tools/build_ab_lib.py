@@ -5,6 +5,12 @@ AB_DIR=tools/<name> picks another directory; HQ_KERNEL_CFLAGS="-DHQ_EPI_DIAG=1 .
 only — the production build never reads it).
 
     python tools/build_ab_lib.py HEAD ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm.hip
+
+A file is overlaid whole, so REV must define the same functions in it as the tree does: across the commit that split
+norm.hip (into norm / embed / sort / rowops.hip, the span head into heads.hip) and moved the fp8 quantisers and amax
+folds from gemm_fp8.hip to fp8.hip, name every file the subject moved between (and include/hq_kernels.h), or the
+link has duplicate or missing hq_* symbols; a subject whose file does not exist at REV (embed / sort / rowops.hip)
+cannot be overlaid from before that commit — build that revision whole in a worktree instead.
 """
 import os
 import shutil

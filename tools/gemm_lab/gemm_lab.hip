@@ -22,6 +22,7 @@ __global__ void fill_rand(uint16_t* p, size_t n, uint32_t seed) {
 }
 
 HqDropKey hq_drop_key(uint32_t seed, uint32_t opid) { return HqDropKey{hq_op_key(seed, opid), opid, nullptr}; }
+int hq_num_cus() { return 256; }   // rowops.hip's, for the stand-alone link
 
 typedef void (*Kern)(const uint16_t*, const uint16_t*, uint16_t*, const float*, uint16_t*, const uint16_t*, float*, int,
                      int, int, int, int, int, HqDropArg);

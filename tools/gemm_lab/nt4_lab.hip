@@ -37,6 +37,7 @@ __global__ void fill_randf(float* p, size_t n, uint32_t seed) {
 }
 
 HqDropKey hq_drop_key(uint32_t seed, uint32_t opid) { return HqDropKey{hq_op_key(seed, opid), opid, nullptr}; }
+int hq_num_cus() { return 256; }   // rowops.hip's, for the stand-alone link
 
 static std::vector<float> to_host_bf16(const uint16_t* d, size_t n) {
   std::vector<uint16_t> h(n);

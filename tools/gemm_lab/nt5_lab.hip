@@ -200,6 +200,7 @@ __global__ void fill_rand(uint16_t* p, size_t n, uint32_t seed) {
 }  // namespace
 
 HqDropKey hq_drop_key(uint32_t seed, uint32_t opid) { return HqDropKey{hq_op_key(seed, opid), opid, nullptr}; }
+int hq_num_cus() { return 256; }   // rowops.hip's, for the stand-alone link
 
 static float bf2f(uint16_t b) { uint32_t u = (uint32_t)b << 16; float f; memcpy(&f, &u, 4); return f; }
 
