@@ -1,0 +1,260 @@
+"""Float64 oracle, rounding emulation and planted mistakes for the attention tests (test_attention_oracle_gpu.py).
+
+Everything here runs on the CPU and takes nothing from a kernel.  Heads are [B, nh, L, 64]; ``unpack_ctx`` /
+``unpack_dqkv`` bring the kernels' token-major outputs into that layout.
+
+``oracle``   exact (float64) softmax attention forward and backward of the bf16 or fp32 inputs with its own lse, ctx
+             and δ, the dropout mask of ``ops.rng.keep_mask``, and beside each output the sum of the absolute values
+             of the terms that were added to form it (the running-error scale A of the per-row bound).
+``emulate``  the same computation in fp32 with the bf16 roundings that csrc/kernels/attention.hip performs.  It is
+             the noise model the bounds of the tests are derived from; it models neither the kernels' accumulation
+             order, nor FMA contraction, nor the hardware's exp2 / log2.
+``MUTANTS``  mistakes planted in the oracle's backward; each must be rejected by the bounds.
+"""
+import functools
+
+import torch
+
+from ml_recipe_distributed_pytorch_amd.ops import rng
+
+D = 64
+NEG = -10000.0
+SCALE = 0.125
+SEED, OPID = 555, 3
+LOG2E = 1.4426950408889634
+LN2 = 0.6931471805599453
+U_BF16 = 2.0 ** -9
+U_F32 = 2.0 ** -24
+
+
+def heads(x, B, L, nh, parts, dtype=torch.float64):
+    """[B·L, parts·nh·64] -> parts tensors [B, nh, L, 64]."""
+    t = x.detach().to(device="cpu", dtype=dtype).view(B, L, parts, nh, D).permute(2, 0, 3, 1, 4)
+    return tuple(t[i] for i in range(parts))
+
+
+def unpack_ctx(ctx, B, L, nh):
+    return heads(ctx, B, L, nh, 1)[0]
+
+
+def unpack_dqkv(dqkv, B, L, nh):
+    return heads(dqkv, B, L, nh, 3)
+
+
+def pack_dqkv(dq, dk, dv):
+    B, nh, L, _ = dq.shape
+    return torch.stack([dq, dk, dv], 0).permute(1, 3, 0, 2, 4).reshape(B * L, 3 * nh * D)
+
+
+# ---------------------------------------------------------------------------------------------- inputs
+def key_bias(B, L, mask, ramp=0.0):
+    """fp32 [B, L] additive key bias: a ramp plus −10000 on the masked keys of pattern ``mask``."""
+    kb = ramp * torch.arange(L, dtype=torch.float32).expand(B, L).clone()
+    if mask in ("tail", "allmasked"):          # right padding of a different length per batch (none if L == 1)
+        for b in range(B):
+            n = min(L - 1, 1 + 7 * b)
+            if n:
+                kb[b, L - n:] = NEG
+    if mask == "left40":                       # crosses the first 32-key tile
+        kb[:, :40] = NEG
+    if mask == "tile":                         # one whole 32-key tile in the middle
+        kb[:, 32:64] = NEG
+    if mask == "one":                          # a single live key, another one per batch
+        for b in range(B):
+            live = (17 * b + 5) % L
+            kb[b, :live] = NEG
+            kb[b, live + 1:] = NEG
+    if mask == "allmasked":                    # batch 1: no live key at all (softmax is shift-invariant)
+        kb[1 % B, :] = NEG
+    return kb
+
+
+def make_inputs(B, L, nh, mask="tail", ramp=0.0, dtype=torch.bfloat16):
+    """(qkv [B·L, 3H], key_bias [B, L] fp32, dctx [B·L, H]): N(0, 1) values in ``dtype``."""
+    g = torch.Generator().manual_seed(3000 + L)
+    H = nh * D
+    qkv = torch.randn(B * L, 3 * H, generator=g).to(dtype)
+    dctx = torch.randn(B * L, H, generator=g).to(dtype)
+    return qkv, key_bias(B, L, mask, ramp), dctx
+
+
+def keep_matrix(B, nh, L, p, seed=SEED, opid=OPID):
+    """bool [B, nh, L, L], or None for p <= 0."""
+    if p <= 0.0:
+        return None
+    return rng.keep_mask((B, nh, L, L), seed, opid, p, device="cpu")
+
+
+# ---------------------------------------------------------------------------------------------- oracle
+MUTANTS = ("seam_key31", "last_valid_key", "dq_gain_1.01", "dq_gain_1.10", "dv_no_keep_scale", "dp_no_keep_scale",
+           "no_delta", "keep_bit_flip")
+
+
+def oracle(qkv, kb, dctx, B, L, nh, p, keep, scale=SCALE, mutant=None):
+    """dict of float64 [B, nh, L, ·]: ctx, lse, dq, dk, dv and the absolute-term sums A_ctx, A_q, A_k, A_v.
+    ``keep``: keep_matrix(B, nh, L, p) (None without dropout)."""
+    assert mutant is None or mutant in MUTANTS
+    q, k, v = heads(qkv, B, L, nh, 3)
+    do = heads(dctx, B, L, nh, 1)[0]
+    kbd = kb.double()
+    s = q @ k.transpose(-1, -2) * scale + kbd[:, None, None, :]
+    lse = torch.logsumexp(s, -1)
+    P = torch.exp(s - lse[..., None])
+    ks = rng.keep_scale(p) if keep is not None else 1.0
+    if keep is not None:
+        keep = keep.double()
+    if mutant == "keep_bit_flip":
+        keep = keep.clone()
+        keep[:, :, 5 % L, 37 % L] = 1.0 - keep[:, :, 5 % L, 37 % L]
+    Pd = P * keep * ks if keep is not None else P
+    ctx = Pd @ v
+    dP = do @ v.transpose(-1, -2)
+    if keep is not None:
+        dP = dP * keep * (1.0 if mutant == "dp_no_keep_scale" else ks)
+    delta = (do * ctx).sum(-1, keepdim=True)
+    dS = P * (dP - (0.0 if mutant == "no_delta" else delta))
+    dSq = dSk = dS
+    if mutant == "seam_key31":                 # a term lost at a tile seam: key 31 × queries 0..31, in dQ and in dK
+        dSq = dS.clone()
+        dSq[:, :, :32, min(31, L - 1)] = 0.0
+        dSk = dSq
+    if mutant == "last_valid_key":             # dQ loses the last live key of its batch
+        dSq = dS.clone()
+        for b in range(B):
+            live = (kbd[b] - kbd[b].max() > NEG / 2).nonzero()
+            dSq[b, :, :, int(live.max())] = 0.0
+    dq = dSq @ k * scale
+    dk = dSk.transpose(-1, -2) @ q * scale
+    Pv = P * keep if (mutant == "dv_no_keep_scale" and keep is not None) else Pd
+    dv = Pv.transpose(-1, -2) @ do
+    if mutant == "dq_gain_1.01":
+        dq = dq * 1.01
+    if mutant == "dq_gain_1.10":
+        dq = dq * 1.10
+    # the terms of dS = P∘dP − P·δ, δ = Σ_d dO_d·ctx_d, by absolute value: |dS| alone would hide the cancellation
+    # inside dS (exact, dS = 0, where one key holds all the mass), which the kernels' δ from a bf16 ctx cannot share
+    dSa = P * (dP.abs() + (do * ctx).abs().sum(-1, keepdim=True))
+    return {"ctx": ctx, "lse": lse, "dq": dq, "dk": dk, "dv": dv,
+            "A_ctx": Pd @ v.abs(), "A_q": dSa @ k.abs() * scale, "A_k": dSa.transpose(-1, -2) @ q.abs() * scale,
+            "A_v": Pd.transpose(-1, -2) @ do.abs()}
+
+
+# ------------------------------------------------------------------------------------------- emulation
+def _bf(x):
+    """fp32 -> nearest bf16 (RNE, as v_cvt_pk_bf16_f32) -> fp32."""
+    return x.bfloat16().float()
+
+
+def _mm(a, b):
+    """fp32 matmul with ONE rounding (float64 product sums): the same figures whatever the BLAS and thread count."""
+    return (a.double() @ b.double()).float()
+
+
+def _exp2(x):
+    """fp32 exp2 as the float64 result rounded once (no dependence on the CPU's vector math library)."""
+    return torch.exp2(x.double()).float()
+
+
+def emulate(qkv, kb, dctx, B, L, nh, p, keep, scale=SCALE):
+    """The bf16 kernels' arithmetic (attention.hip) in fp32 tensors — every elementwise result rounded to fp32 as in
+    the VALU code, every matmul once as an MFMA accumulator (``_mm``) — with the kernels' bf16 roundings:
+
+    * Q·c rounded to bf16 with c = scale·log2e in fp32 (``prescale8``; hq_attn_fwd / hq_attn_bwd pass
+      ``scale * LOG2E`` as a float: c itself is not rounded to bf16);
+    * the key bias as bf16 hi + bf16 lo of bias·log2e (the ``sA`` words of each prologue, ``kaug``);
+    * m = the true row max, as on the forward's slow path (the fast path keeps the first tile's bf16-rounded max,
+      which moves the binade of P and l, not their relative rounding);
+    * P rounded to bf16 as the MFMA operand of P·V (``pack_b``), l summed from the unrounded fp32 P (``l2``);
+    * ctx = bf16(O·(ks/l)) (``store_tile64_lines``), lse = (m + log2 l)·ln2;
+    * backward: P = exp2(S' − lse·log2e) with lse riding the score MFMA to ~24 bits (``split3``),
+      δ = rowsum(dO·ctx) from the bf16 ctx (``dpart``), dS = (dP·keep·ks − δ)·P rounded to bf16 (``pack_b``),
+      P∘keep rounded to bf16 for dV, dK = ln2·dSᵀ·(the rounded Q·c), and dQ, dK, dV rounded to bf16 on store.
+    Returns ctx, lse, dq, dk, dv as float64 [B, nh, L, ·]."""
+    f32 = torch.float32
+    q, k, v = heads(qkv, B, L, nh, 3, f32)
+    do = heads(dctx, B, L, nh, 1, f32)[0]
+    c = torch.tensor(scale, dtype=f32) * torch.tensor(LOG2E, dtype=f32)
+    qc = _bf(q * c)
+    bl = kb.float() * torch.tensor(LOG2E, dtype=f32)
+    bhi = _bf(bl)
+    bias = (bhi + _bf(bl - bhi))[:, None, None, :]
+    s2 = _mm(qc, k.transpose(-1, -2)) + bias
+    m = s2.max(-1, keepdim=True).values
+    Pu = _exp2(s2 - m)
+    l = Pu.sum(-1, keepdim=True)
+    ks = torch.tensor(rng.keep_scale(p) if keep is not None else 1.0, dtype=f32)
+    Pb = _bf(Pu)
+    if keep is not None:
+        Pb = Pb * keep
+    ctx = _bf(_mm(Pb, v) * (ks / l))
+    lse = (m + torch.log2(l.double()).float()) * torch.tensor(LN2, dtype=f32)
+    # backward, from the emulated ctx and lse (as the kernels read the forward's)
+    P = _exp2(s2 - lse * torch.tensor(LOG2E, dtype=f32))
+    dP = _mm(do, v.transpose(-1, -2))
+    if keep is not None:
+        dP = dP * keep * ks
+    delta = (do * ctx).sum(-1, keepdim=True)
+    dS = _bf((dP - delta) * P)
+    dq = _bf(_mm(dS, k) * torch.tensor(scale, dtype=f32))
+    dk = _bf(_mm(dS.transpose(-1, -2), qc) * torch.tensor(LN2, dtype=f32))
+    Pm = _bf(P)
+    if keep is not None:
+        Pm = Pm * keep
+    dv = _bf(_mm(Pm.transpose(-1, -2), do) * ks)
+    out = {"ctx": ctx, "lse": lse.squeeze(-1), "dq": dq, "dk": dk, "dv": dv}
+    return {n: t.double() for n, t in out.items()}
+
+
+# --------------------------------------------------------------------------------------------- metrics
+OUTPUTS = (("ctx", "A_ctx"), ("dq", "A_q"), ("dk", "A_k"), ("dv", "A_v"))
+
+
+def row_ratio(x, ref, A, u, tiny):
+    """Worst over the rows (64-vectors) of (‖x − ref‖₂ − tiny) / (u·‖A‖₂): the per-row bound holds with the
+    constant K iff this is <= K.  A row with A = 0 must agree within ``tiny`` (it then counts 0, else inf)."""
+    err = (x - ref).norm(dim=-1) - tiny
+    a = u * A.norm(dim=-1)
+    r = torch.where(err <= 0, torch.zeros_like(err), err / a)      # x / 0 = inf for x > 0; NaN stays NaN
+    return float(r.max()) if not bool(torch.isnan(r).any()) else float("nan")
+
+
+def negligible(ref, A, u):
+    """An output that cancels to less than its own rounding scale as a whole (dQ, dK where one key holds all the
+    mass: dS = 0 exactly): relative aggregate figures say nothing about it, the per-row bound still holds."""
+    return float(ref.norm()) <= u * float(A.norm())
+
+
+def rel_frobenius(x, ref):
+    return float((x - ref).norm()) / float(ref.norm())
+
+
+def gain(x, ref):
+    """The coherent part of the error, <x − ref, ref> / <ref, ref>: 0.01 for an output scaled by 1.01."""
+    return float(((x - ref) * ref).sum()) / float((ref * ref).sum())
+
+
+def measure(got, orc, u, tiny):
+    """{output: (worst per-row ratio, relative Frobenius error, |gain|)}; the two aggregates are 0 for a
+    ``negligible`` output."""
+    res = {}
+    for n, a in OUTPUTS:
+        agg = (0.0, 0.0) if negligible(orc[n], orc[a], u) else \
+            (rel_frobenius(got[n], orc[n]), abs(gain(got[n], orc[n])))
+        res[n] = (row_ratio(got[n], orc[n], orc[a], u, tiny),) + agg
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def bf16_case(B, L, nh, p, mask, ramp):
+    """(inputs, oracle, emulation) of one bf16 case, computed once per process and shared by every test that
+    needs it: read-only."""
+    inp = make_inputs(B, L, nh, mask, ramp)
+    keep = keep_matrix(B, nh, L, p)
+    return inp, oracle(*inp, B, L, nh, p, keep), emulate(*inp, B, L, nh, p, keep)
+
+
+@functools.lru_cache(maxsize=None)
+def f32_case(B, L, nh, p):
+    """(fp32 inputs, oracle) of one case of the fp32 flash attention."""
+    inp = make_inputs(B, L, nh, "tail", 0.0, torch.float32)
+    return inp, oracle(*inp, B, L, nh, p, keep_matrix(B, nh, L, p))
