@@ -48,7 +48,7 @@ def main(params, model_params) -> Predictor:
     dataset = get_validation_dataset(params, tokenizer=tokenizer)
     predictor = Predictor(model, device, collate_fun=factories.init_collate_fun(tokenizer, return_items=True),
                           batch_size=params.batch_size, n_jobs=params.n_jobs, buffer_size=params.buffer_size,
-                          limit=params.limit)
+                          limit=params.limit, span_decode=params.span_decode, max_answer_len=params.max_answer_len)
     predictor(dataset)
     m = predictor.metrics()
     logger.info("Validation metrics: " + ", ".join(f"{k}: {v:.4f}" if isinstance(v, float) else f"{k}: {v}"

@@ -762,6 +762,50 @@ std::vector<Tensor> qa_heads_fwd(Tensor seq, int64_t L, std::vector<Tensor> w, d
   return {logits, pooled, cls, reg};
 }
 
+// Joint valid-span decode (decode.hip).  start / end [B, L], cls [B, NL], start_reg / end_reg [B] are read in place
+// through their strides (under no_grad the fused heads hand out stride-2 views of the logits and reg buffers).
+HqDecodeIn decode_in(const Tensor& start, const Tensor& end, const Tensor& cls, const Tensor& start_reg,
+                     const Tensor& end_reg, const Tensor& lo, const Tensor& hi) {
+  TORCH_CHECK(start.is_cuda(), "qa_decode: start must be a GPU tensor");
+  for (const Tensor* t : {&end, &cls, &start_reg, &end_reg, &lo, &hi})
+    TORCH_CHECK(t->device() == start.device(), "qa_decode: all tensors must be on one device, got ", t->device(),
+                " and ", start.device());
+  for (const Tensor* t : {&start, &end, &cls, &start_reg, &end_reg})
+    TORCH_CHECK(t->scalar_type() == F32, "qa_decode: logits and regs must be fp32, got ", t->scalar_type());
+  TORCH_CHECK(start.dim() == 2 && end.dim() == 2 && cls.dim() == 2, "qa_decode: start / end [B, L], cls [B, NL]");
+  const int64_t B = start.size(0), L = start.size(1), NL = cls.size(1);
+  TORCH_CHECK(end.size(0) == B && end.size(1) == L && cls.size(0) == B, "qa_decode: start, end, cls disagree on B or L");
+  TORCH_CHECK(L >= 1 && L <= kHqDecodeMaxL, "qa_decode supports 1 <= L <= ", kHqDecodeMaxL, ", got ", L);
+  TORCH_CHECK(NL >= 1 && NL <= 8, "qa_decode supports 1..8 classes, got ", NL);
+  TORCH_CHECK(start_reg.dim() == 1 && end_reg.dim() == 1 && start_reg.numel() == B && end_reg.numel() == B,
+              "qa_decode: start_reg / end_reg must be [B]");
+  TORCH_CHECK(lo.scalar_type() == at::kInt && hi.scalar_type() == at::kInt, "qa_decode: lo / hi must be int32, got ",
+              lo.scalar_type(), " and ", hi.scalar_type());
+  TORCH_CHECK(lo.is_contiguous() && hi.is_contiguous() && lo.numel() == B && hi.numel() == B,
+              "qa_decode: lo / hi must be contiguous with B elements");
+  HqDecodeIn in;
+  in.start = ptr<float>(start); in.end = ptr<float>(end); in.cls = ptr<float>(cls);
+  in.start_reg = ptr<float>(start_reg); in.end_reg = ptr<float>(end_reg);
+  in.lo = ptr<int32_t>(lo); in.hi = ptr<int32_t>(hi);
+  in.start_row = start.stride(0); in.start_elem = start.stride(1);
+  in.end_row = end.stride(0); in.end_elem = end.stride(1);
+  in.cls_row = cls.stride(0); in.cls_elem = cls.stride(1);
+  in.start_reg_elem = start_reg.stride(0); in.end_reg_elem = end_reg.stride(0);
+  return in;
+}
+
+// returns [B, 6] fp32 = (score, start, end, start_reg, end_reg, label)
+Tensor qa_decode(Tensor start, Tensor end, Tensor cls, Tensor start_reg, Tensor end_reg, Tensor lo, Tensor hi, int64_t W) {
+  const HqDecodeIn in = decode_in(start, end, cls, start_reg, end_reg, lo, hi);
+  TORCH_CHECK(W >= 1, "qa_decode: max answer length must be >= 1, got ", W);
+  const int64_t B = start.size(0), L = start.size(1);
+  c10::DeviceGuard g(start.device());
+  auto out = at::empty({B, 6}, start.options());
+  if (B == 0) return out;
+  hq_qa_decode(in, ptr<float>(out), (int)B, (int)L, (int)cls.size(1), (int)std::min<int64_t>(W, L), cur_stream());
+  return out;
+}
+
 // returns losses [6], dlog [T,2], dheads [B,16]
 std::vector<Tensor> qa_loss(Tensor logits, Tensor cls, Tensor reg, Tensor t_start, Tensor t_end, Tensor t_rs, Tensor t_re,
                             Tensor t_cls, c10::optional<Tensor> lw, int64_t kind, int64_t ignore_cls,
@@ -1099,6 +1143,12 @@ PYBIND11_MODULE(_hq_kernels, m) {
     }
   });
   m.def("qa_heads_fwd", &qa_heads_fwd);
+  m.def("qa_decode", &qa_decode);
+  // tests: whether these inputs take the kernel's 8-byte interleaved loads (else scalar strided loads)
+  m.def("qa_decode_interleaved", [](Tensor start, Tensor end, Tensor cls, Tensor start_reg, Tensor end_reg, Tensor lo,
+                                    Tensor hi) {
+    return hq_qa_decode_interleaved(decode_in(start, end, cls, start_reg, end_reg, lo, hi));
+  });
   m.def("qa_loss", &qa_loss);
   m.def("qa_heads_bwd", &qa_heads_bwd);
   m.def("gelu_bwd", &gelu_bwd);

@@ -306,3 +306,19 @@ void hq_qa_heads_bwd(const void* seq, const float* dlog, const float* dheads, co
                      const float* reg, const HqHeadWeights& w, const HqHeadGrads& g, void* dseq, float* span_part,
                      int B, int L, int H, int NL, bool accumulate, float p, uint32_t seed, uint32_t opid, hipStream_t s,
                      bool seq_f32 = false, float* dpre = nullptr);   // dpre: [B][H] scratch (dL/d pooler pre-activation)
+
+// ------------------------------------------------------------------ decode.hip: joint valid-span decoding
+// Per row b the best span (s, e) with clamp(lo) <= s <= e < clamp(hi), e - s < W by key = start[s] + end[e] (one
+// rounded fp32 add; ties: smallest s, then smallest e), score = key - (start[0] + end[0]), label = first argmax of
+// cls[b, :NL]; out[b] = (score, s, e, start_reg, end_reg, label), an empty window gives (-inf, -1, -1, ...).
+// Every input is read in place through element strides: row / elem for the [B, L] logits and cls, one for the regs.
+constexpr int kHqDecodeMaxL = 512;
+struct HqDecodeIn {
+  const float *start, *end, *cls, *start_reg, *end_reg;
+  const int32_t *lo, *hi;   // [B] contiguous, clamped to [0, L] in the kernel
+  long long start_row, start_elem, end_row, end_elem, cls_row, cls_elem, start_reg_elem, end_reg_elem;
+};
+// start and end are the two halves of one interleaved [B, L, 2] buffer whose rows are all 8-byte aligned: the
+// kernel fetches both logits of a position with one 8-byte load (same result as the scalar loads)
+bool hq_qa_decode_interleaved(const HqDecodeIn& in);
+void hq_qa_decode(const HqDecodeIn& in, float* out, int B, int L, int NL, int W, hipStream_t s);

@@ -1,10 +1,20 @@
 """Chunked QA inference (reference ``modules/model/inference/predictor.py:14-144``).
 
-For every chunk of every document: argmax start / end logits, softmax-argmax class, and the
-score of arXiv:1901.08634 ``max_start + max_end − (start[CLS] + end[CLS])``.  Per document the best
-*valid* chunk wins (start ≤ end, start inside the document part ``≥ question_len + 2``, score not
-below the best so far).  Scoring is vectorised per batch on device; a single device→host copy per
-batch carries everything the candidate update needs.
+Two span-decoding rules, chosen by ``span_decode``:
+
+* ``"argmax"`` (default; the reference's rule, outputs unchanged): per chunk the argmax of the start logits and the
+  argmax of the end logits, taken *independently*, softmax-argmax class, and the score
+  ``max_start + max_end − (start[CLS] + end[CLS])``.  This is a shortcut, not the rule of arXiv:1901.08634: the two
+  maxima need not form a span, and a chunk whose pair is invalid (start after end, or start inside the question,
+  ``< question_len + 2``) is dropped.  Per document the best valid chunk wins (score not below the best so far).
+* ``"joint"`` (the paper's rule): per chunk the maximum of ``start[s] + end[e]`` over the *valid* spans only — both
+  ends inside the document part ``[question_len + 2, len(input_ids) − 1)``, ``s ≤ e``, at most ``max_answer_len``
+  tokens — minus ``start[CLS] + end[CLS]`` (``ops.qa_decode``: one HIP kernel on the GPU, ``ops.reference`` on the
+  CPU, bit-identical).  Every chunk with a non-empty document part yields a candidate; a negative score (the model
+  prefers "no answer" for that chunk) is legal, and the document keeps its best span.
+
+Either way scoring runs per batch on device; a single device→host copy per batch carries everything the
+candidate update needs.
 
 Additions (D12): ``metrics()`` — label accuracy, span exact-match / token-F1 against the true
 document-token span, and coverage — and ``predicted_text`` for ``show_predictions``.
@@ -20,11 +30,18 @@ from typing import Dict, Optional
 import numpy as np
 import torch
 
+from .. import ops
 from ..data.items import ID2LABELS
 from ..data.list_loader import ListDataloader
 from ..train.engine import to_device
 
 logger = logging.getLogger(__name__)
+
+SPAN_DECODE_MODES = ("argmax", "joint")
+
+
+def _neg_inf() -> float:
+    return float("-inf")
 
 
 @dataclass
@@ -45,11 +62,17 @@ def doc_span(item, start_id: int, end_id: int):
 
 class Predictor:
     def __init__(self, model, device, *, batch_size=256, n_jobs=16, collate_fun=None, buffer_size=4096, limit=None,
-                 timeout_s: float = 600.0):
+                 timeout_s: float = 600.0, span_decode: str = "argmax", max_answer_len: int = 30):
+        if span_decode not in SPAN_DECODE_MODES:
+            raise ValueError(f"span_decode must be one of {SPAN_DECODE_MODES}, got {span_decode!r}")
+        if int(max_answer_len) < 1:
+            raise ValueError(f"max_answer_len must be >= 1, got {max_answer_len}")
+        self.span_decode, self.max_answer_len = span_decode, int(max_answer_len)
         self.model = model
         self.device = torch.device(device)
         self.model.to(self.device)
-        self.scores: Dict[str, float] = defaultdict(float)
+        # a document's running best: 0.0 under the argmax rule (its scores are >= 0), -inf under the joint rule
+        self.scores: Dict[str, float] = defaultdict(float if span_decode == "argmax" else _neg_inf)
         self.candidates: Dict[str, PredictorCandidate] = {}
         self.items = {}
         self.batch_size, self.n_jobs, self.collate_fun = batch_size, n_jobs, collate_fun
@@ -85,6 +108,25 @@ class Predictor:
                            preds["end_reg"].float().reshape(-1), cls_id.float()], 1)
         return out.double().cpu().numpy()
 
+    def decode_batch(self, preds, items) -> np.ndarray:
+        """Joint valid-span decode → one [B, 6] float64 host array (score, start, end, sreg, ereg, cls).  The window
+        of chunk b is its document part: from ``question_len + 2`` (the start ``_is_valid`` and ``doc_span`` use, for
+        both model families) up to ``len(input_ids) − 1`` (the final separator and all padding excluded)."""
+        dev = preds["start_class"].device
+        lo = torch.tensor([it.question_len + 2 for it in items], dtype=torch.int32).to(dev)
+        hi = torch.tensor([len(it.input_ids) - 1 for it in items], dtype=torch.int32).to(dev)
+        out = ops.qa_decode(preds["start_class"], preds["end_class"], preds["cls"], preds["start_reg"],
+                            preds["end_reg"], lo, hi, self.max_answer_len)
+        return out.double().cpu().numpy()
+
+    def _update_candidates_joint(self, r, items):
+        for (sc, s, e, sr, er, lb), item in zip(r, items):
+            if s < 0 or self.scores[item.item_id] > sc:   # empty window, or the stored score is strictly greater
+                continue
+            self.scores[item.item_id] = float(sc)
+            self.candidates[item.item_id] = PredictorCandidate(int(s), int(e), float(sr), float(er), int(lb), float(sc))
+            self.items[item.item_id] = item
+
     @torch.no_grad()
     def __call__(self, dataset, *, save_dump=False):
         self.model.eval()
@@ -94,10 +136,15 @@ class Predictor:
             self.dump = []
         for batch_i, (inputs, _labels, items) in enumerate(loader):
             inputs = to_device(inputs, self.device)
-            r = self.score_batch(self.model(**inputs))
+            preds = self.model(**inputs)
             self.n_chunks += len(items)
-            self._update_candidates(r[:, 0], r[:, 1].astype(np.int64), r[:, 2].astype(np.int64), r[:, 3], r[:, 4],
-                                    r[:, 5].astype(np.int64), items)
+            if self.span_decode == "joint":
+                r = self.decode_batch(preds, items)
+                self._update_candidates_joint(r, items)
+            else:
+                r = self.score_batch(preds)
+                self._update_candidates(r[:, 0], r[:, 1].astype(np.int64), r[:, 2].astype(np.int64), r[:, 3], r[:, 4],
+                                        r[:, 5].astype(np.int64), items)
             if save_dump:
                 self.dump.append((r[:, 0], r[:, 1].astype(np.int64), r[:, 2].astype(np.int64),
                                   r[:, 5].astype(np.int64), [it.item_id for it in items]))
@@ -151,5 +198,9 @@ class Predictor:
         out = {str(k): {"label": ID2LABELS[c.label], "score": c.score, "start_id": c.start_id, "end_id": c.end_id,
                         "start_reg": c.start_reg, "end_reg": c.end_reg, "text": self.predicted_text(k)}
                for k, c in self.candidates.items()}
+        doc = {"metrics": self.metrics()}
+        if self.span_decode != "argmax":   # the argmax file stays byte for byte what it was
+            doc.update(span_decode=self.span_decode, max_answer_len=self.max_answer_len)
+        doc["predictions"] = out
         with open(path, "w") as f:
-            json.dump({"metrics": self.metrics(), "predictions": out}, f, indent=1)
+            json.dump(doc, f, indent=1)

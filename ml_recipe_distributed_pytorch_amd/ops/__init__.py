@@ -493,3 +493,15 @@ def bias_grad(dy, g_b, accumulate):
     if _hip(dy):
         return _k().bias_grad(dy, g_b, bool(accumulate))
     ref._acc(g_b, dy.float().sum(0), accumulate)
+
+
+# ------------------------------------------------------------------------------------ inference decode
+def qa_decode(start, end, cls, start_reg, end_reg, lo, hi, max_answer_len: int):
+    """Joint valid-span decode of a batch of chunks → fp32 ``[B, 6]`` (score, start, end, start_reg, end_reg, label);
+    see ``ops.reference.qa_decode`` for the definition.  GPU tensors run ``decode.hip`` and are read in place
+    through their strides (the fused heads' stride-2 views are not copied); CPU tensors run the reference."""
+    start, end, cls, start_reg, end_reg = (t if t.dtype == torch.float32 else t.float()
+                                           for t in (start, end, cls, start_reg, end_reg))
+    if start.is_cuda:
+        return _k().qa_decode(start, end, cls, start_reg.reshape(-1), end_reg.reshape(-1), lo, hi, int(max_answer_len))
+    return ref.qa_decode(start, end, cls, start_reg, end_reg, lo, hi, max_answer_len)

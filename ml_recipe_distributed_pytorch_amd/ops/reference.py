@@ -282,3 +282,40 @@ def adamod_step(master, compute, grad, exp_avg, exp_avg_sq, exp_avg_lr, segments
     if compute is not None and compute.data_ptr() != master.data_ptr():
         for start, numel, _ in segments:
             compute[start:start + numel].copy_(master[start:start + numel])
+
+
+# ------------------------------------------------------------------------------------ inference decode
+def qa_decode(start, end, cls, start_reg, end_reg, lo, hi, max_answer_len: int) -> Tensor:
+    """Joint valid-span decode, the definition ``csrc/kernels/decode.hip`` implements bit for bit.
+
+    Per row: window ``lo' = clamp(lo, 0, L)``, ``hi' = clamp(hi, 0, L)``; candidates ``lo' <= s <= e < hi'`` with
+    ``e - s < max_answer_len``; ``key = fl32(start[s] + end[e])``; the largest key wins, then the smallest ``s``,
+    then the smallest ``e``; ``score = fl32(key - fl32(start[0] + end[0]))``; no candidate → ``s = e = -1``,
+    ``score = -inf``; ``label`` = first argmax of ``cls``.  Returns fp32 ``[B, 6]`` = (score, s, e, start_reg,
+    end_reg, label).  Ties are resolved by the smallest flat index among the maxima, never by ``argmax``, whose
+    choice among equal values differs between devices.
+    """
+    W = int(max_answer_len)
+    if W < 1:
+        raise ValueError(f"max_answer_len must be >= 1, got {max_answer_len}")
+    start, end, cls = start.float(), end.float(), cls.float()
+    B, L = start.shape
+    dev = start.device
+    lo = lo.to(dev).long().clamp(0, L).view(B, 1, 1)
+    hi = hi.to(dev).long().clamp(0, L).view(B, 1, 1)
+    s = torch.arange(L, device=dev).view(1, L, 1)
+    e = torch.arange(L, device=dev).view(1, 1, L)
+    valid = ((s >= lo) & (e < hi) & (e >= s) & (e - s < W)).view(B, L * L)
+    key = (start.unsqueeze(2) + end.unsqueeze(1)).view(B, L * L)
+    best = torch.where(valid, key, key.new_full((), float("-inf"))).amax(1)
+    flat = torch.arange(L * L, device=dev).expand(B, L * L)
+    first = torch.where(valid & (key == best.unsqueeze(1)), flat, flat.new_full((), L * L)).amin(1)
+    found = first < L * L
+    s_id = torch.where(found, first // L, first.new_full((), -1))
+    e_id = torch.where(found, first % L, first.new_full((), -1))
+    score = torch.where(found, best - (start[:, 0] + end[:, 0]), best.new_full((), float("-inf")))
+    NL = cls.shape[1]
+    c = torch.arange(NL, device=dev).expand(B, NL)
+    label = torch.where(cls == cls.amax(1, keepdim=True), c, c.new_full((), NL)).amin(1)
+    return torch.stack([score, s_id.float(), e_id.float(), start_reg.float().reshape(-1), end_reg.float().reshape(-1),
+                        label.float()], 1)

@@ -240,4 +240,9 @@ def get_predictor_parser() -> ArgumentParser:
     # --- MI355X additions -------------------------------------------------------------------
     parser.add_argument("--dummy_dataset", action="store_true", help="Validate on generated chunks (no NQ data).")
     parser.add_argument("--dump_predictions", type=cast2(str), default=None, help="Write predictions JSON here.")
+    parser.add_argument("--span_decode", type=str, default="argmax", choices=["argmax", "joint"],
+                        help="Span decoding rule: the reference's independent start / end argmax, or the joint "
+                             "maximum over valid document spans of bounded length (arXiv:1901.08634).")
+    parser.add_argument("--max_answer_len", type=int, default=30,
+                        help="Maximum answer length in tokens for --span_decode joint (arXiv:1901.08634 uses 30).")
     return parser
