@@ -140,7 +140,8 @@ def run_worker(local_idx, plan, params, model_params):
         logger.error("Training process was interrupted.")
         trainer.save_state_dict(out_dir / "interrupt.ch")
     finally:
-        signal.signal(signal.SIGTERM, prev)
+        if prev is not None:   # None: the earlier handler was installed from C (under rocprofv3) and cannot be put back
+            signal.signal(signal.SIGTERM, prev)
         if trainer.reducer is not None:
             trainer.reducer.close()
         if trainer.writer is not None:

@@ -697,6 +697,133 @@ void adamod(Tensor master, c10::optional<Tensor> compute, Tensor grad, Tensor m,
             HqBeta(beta2), HqBeta(beta3), (float)eps, (float)bias_corr, optr<float>(clip_coef), cur_stream());
 }
 
+// LAMB.  The kernels trust their tables, so the tables are checked ONCE, on the host, where they are built:
+// lamb_plan takes the chunk table and seg_first_chunk as CPU tensors, validates every row against the arena, derives
+// the per-chunk segment index and uploads all three.  The step bindings accept only such a plan and check the arenas
+// against it, so a bad table or shape raises before any launch and a step never reads a table back.
+struct LambPlan {
+  Tensor chunks, seg_first_chunk, chunk_seg;   // device: int64 [nchunks,2], int32 [nseg+1], int32 [nchunks]
+  int64_t arena_numel = 0;
+  int64_t nchunks = 0, nseg = 0, ngroups = 0;
+};
+
+LambPlan lamb_plan(Tensor master, Tensor chunks, Tensor seg_first_chunk) {
+  check(master, F32, "master");
+  TORCH_CHECK(!chunks.is_cuda() && chunks.scalar_type() == I64 && chunks.is_contiguous() && chunks.dim() == 2 &&
+                  chunks.size(1) == 2, "chunks must be a CPU [n,2] int64 tensor");
+  TORCH_CHECK(!seg_first_chunk.is_cuda() && seg_first_chunk.scalar_type() == at::kInt && seg_first_chunk.is_contiguous() &&
+                  seg_first_chunk.dim() == 1, "seg_first_chunk must be a CPU int32 vector");
+  const int64_t nc = chunks.size(0), ns = seg_first_chunk.size(0) - 1, N = master.numel();
+  TORCH_CHECK(nc >= 1 && nc < (int64_t)std::numeric_limits<int32_t>::max() / 2, "chunk count");
+  TORCH_CHECK(ns >= 1 && ns <= nc, "seg_first_chunk must have nseg + 1 entries, 1 <= nseg <= nchunks");
+  const auto* c = reinterpret_cast<const HqOptChunk*>(chunks.data_ptr());
+  const int32_t* first = seg_first_chunk.data_ptr<int32_t>();
+  TORCH_CHECK(first[0] == 0 && first[ns] == nc, "seg_first_chunk does not match the chunk table: must run from 0 to nchunks");
+  auto chunk_seg = at::empty({nc}, seg_first_chunk.options());
+  int32_t* cs = chunk_seg.data_ptr<int32_t>();
+  int64_t ngroups = 0, prev_end = 0;
+  for (int64_t s = 0; s < ns; ++s) {
+    TORCH_CHECK(first[s] < first[s + 1] && first[s + 1] <= nc, "seg_first_chunk does not match the chunk table: segment ", s,
+                " is empty or out of range");
+    for (int64_t i = first[s]; i < first[s + 1]; ++i) {
+      TORCH_CHECK(c[i].group >= 0 && c[i].group < kOptMaxGroups, "chunk ", i, ": group index ", c[i].group, " >= ",
+                  kOptMaxGroups);
+      TORCH_CHECK(c[i].numel >= 1 && c[i].numel <= kOptChunk, "chunk ", i, ": numel ", c[i].numel);
+      TORCH_CHECK(c[i].start >= prev_end && c[i].start <= N - c[i].numel, "chunk ", i, " [", c[i].start, ", +", c[i].numel,
+                  ") overlaps its predecessor or lies outside the arena of ", N);
+      if (i > first[s])
+        TORCH_CHECK(c[i].start == prev_end && c[i].group == c[i - 1].group, "seg_first_chunk does not match the chunk "
+                    "table: chunk ", i, " does not continue segment ", s);
+      prev_end = c[i].start + c[i].numel;
+      ngroups = std::max<int64_t>(ngroups, c[i].group + 1);
+      cs[i] = (int32_t)s;
+    }
+  }
+  LambPlan p;
+  p.chunks = chunks.to(master.device());
+  p.seg_first_chunk = seg_first_chunk.to(master.device());
+  p.chunk_seg = chunk_seg.to(master.device());
+  p.arena_numel = N; p.nchunks = nc; p.nseg = ns; p.ngroups = ngroups;
+  return p;
+}
+
+HqLambGroups lamb_groups(const LambPlan& plan, const std::vector<double>& lr, const std::vector<double>& wd,
+                         const std::vector<bool>& adapt) {
+  TORCH_CHECK(lr.size() == wd.size() && lr.size() == adapt.size() && lr.size() <= (size_t)kOptMaxGroups,
+              "at most 8 param groups, lr / wd / adapt of one length");
+  TORCH_CHECK((int64_t)lr.size() >= plan.ngroups, "the chunk table uses ", plan.ngroups, " groups, got ", lr.size());
+  HqLambGroups gr{};
+  for (size_t i = 0; i < lr.size(); ++i) { gr.lr[i] = (float)lr[i]; gr.wd[i] = (float)wd[i]; gr.adapt[i] = adapt[i] ? 1 : 0; }
+  return gr;
+}
+
+void lamb_check_arena(const LambPlan& plan, const Tensor& t, at::ScalarType dt, const char* name) {
+  check(t, dt, name);
+  TORCH_CHECK(t.numel() == plan.arena_numel, name, " has ", t.numel(), " elements, the plan was made for ", plan.arena_numel);
+  TORCH_CHECK(t.device() == plan.chunks.device(), name, " is not on the plan's device");
+}
+void lamb_check_scratch(const LambPlan& plan, const Tensor& partials, const Tensor& norms) {
+  check(partials, F32, "partials"); check(norms, F32, "norms");
+  TORCH_CHECK(partials.numel() == 2 * plan.nchunks && norms.numel() == 3 * plan.nseg,
+              "partials must be [nchunks,2] and norms [nseg,3]");
+  TORCH_CHECK(partials.device() == plan.chunks.device() && norms.device() == plan.chunks.device(), "scratch device");
+}
+
+// bc1 = 1/(1 − β1^t), bc2 = 1/(1 − β2^t) (or 1): doubles from the caller, rounded once here
+void lamb_moments(const LambPlan& plan, Tensor master, Tensor grad, Tensor m, Tensor v, std::vector<double> lr,
+                  std::vector<double> wd, std::vector<bool> adapt, double beta1, double beta2, double eps, double bc1,
+                  double bc2, c10::optional<Tensor> clip_coef, Tensor partials, Tensor norms) {
+  lamb_check_arena(plan, master, F32, "master"); lamb_check_arena(plan, grad, F32, "grad");
+  lamb_check_arena(plan, m, F32, "exp_avg"); lamb_check_arena(plan, v, F32, "exp_avg_sq");
+  check_opt(clip_coef, F32, "clip");
+  lamb_check_scratch(plan, partials, norms);
+  const HqLambGroups gr = lamb_groups(plan, lr, wd, adapt);
+  c10::DeviceGuard g(master.device());
+  hq_lamb_moments(ptr<float>(master), ptr<float>(grad), ptr<float>(m), ptr<float>(v),
+                  reinterpret_cast<const HqOptChunk*>(plan.chunks.data_ptr()), (int)plan.nchunks, gr,
+                  HqLambArgs(HqBeta(beta1), HqBeta(beta2), (float)eps, (float)bc1, (float)bc2), optr<float>(clip_coef),
+                  ptr<float>(partials), cur_stream());
+}
+
+void lamb_ratio(const LambPlan& plan, std::vector<double> lr, std::vector<double> wd, std::vector<bool> adapt,
+                Tensor partials, Tensor norms) {
+  lamb_check_scratch(plan, partials, norms);
+  const HqLambGroups gr = lamb_groups(plan, lr, wd, adapt);
+  c10::DeviceGuard g(partials.device());
+  hq_lamb_ratio(ptr<float>(partials), reinterpret_cast<const HqOptChunk*>(plan.chunks.data_ptr()),
+                plan.seg_first_chunk.data_ptr<int32_t>(), (int)plan.nseg, gr, ptr<float>(norms), cur_stream());
+}
+
+void lamb_apply(const LambPlan& plan, Tensor master, c10::optional<Tensor> compute, Tensor m, Tensor v,
+                std::vector<double> lr, std::vector<double> wd, std::vector<bool> adapt, double beta1, double beta2,
+                double eps, double bc1, double bc2, Tensor partials, Tensor norms) {
+  lamb_check_arena(plan, master, F32, "master");
+  if (has(compute)) lamb_check_arena(plan, *compute, BF16, "compute");
+  lamb_check_arena(plan, m, F32, "exp_avg"); lamb_check_arena(plan, v, F32, "exp_avg_sq");
+  lamb_check_scratch(plan, partials, norms);
+  const HqLambGroups gr = lamb_groups(plan, lr, wd, adapt);
+  c10::DeviceGuard g(master.device());
+  hq_lamb_apply(ptr<float>(master), optr<uint16_t>(compute), ptr<float>(m), ptr<float>(v),
+                reinterpret_cast<const HqOptChunk*>(plan.chunks.data_ptr()), plan.chunk_seg.data_ptr<int32_t>(),
+                (int)plan.nchunks, gr, HqLambArgs(HqBeta(beta1), HqBeta(beta2), (float)eps, (float)bc1, (float)bc2),
+                ptr<float>(norms), cur_stream());
+}
+
+// the whole step: every argument is checked before the first of the three launches
+void lamb_step(const LambPlan& plan, Tensor master, c10::optional<Tensor> compute, Tensor grad, Tensor m, Tensor v,
+               std::vector<double> lr, std::vector<double> wd, std::vector<bool> adapt, double beta1, double beta2,
+               double eps, double bc1, double bc2, c10::optional<Tensor> clip_coef, Tensor partials, Tensor norms) {
+  lamb_check_arena(plan, master, F32, "master"); lamb_check_arena(plan, grad, F32, "grad");
+  if (has(compute)) lamb_check_arena(plan, *compute, BF16, "compute");
+  lamb_check_arena(plan, m, F32, "exp_avg"); lamb_check_arena(plan, v, F32, "exp_avg_sq");
+  check_opt(clip_coef, F32, "clip");
+  lamb_check_scratch(plan, partials, norms);
+  lamb_groups(plan, lr, wd, adapt);
+  lamb_moments(plan, master, grad, m, v, lr, wd, adapt, beta1, beta2, eps, bc1, bc2, clip_coef, partials, norms);
+  lamb_ratio(plan, lr, wd, adapt, partials, norms);
+  lamb_apply(plan, master, compute, m, v, lr, wd, adapt, beta1, beta2, eps, bc1, bc2, partials, norms);
+}
+
 void cast_f32_bf16(Tensor src, Tensor dst, double scale) {
   check(src, F32, "src"); check(dst, BF16, "dst");
   TORCH_CHECK(src.numel() == dst.numel(), "size");
@@ -1187,6 +1314,19 @@ PYBIND11_MODULE(_hq_kernels, m) {
   });
   m.def("adamw", &adamw);
   m.def("adamod", &adamod);
+  py::class_<LambPlan>(m, "LambPlan")
+      .def_readonly("chunks", &LambPlan::chunks)
+      .def_readonly("seg_first_chunk", &LambPlan::seg_first_chunk)
+      .def_readonly("chunk_seg", &LambPlan::chunk_seg)
+      .def_readonly("arena_numel", &LambPlan::arena_numel)
+      .def_readonly("nchunks", &LambPlan::nchunks)
+      .def_readonly("nseg", &LambPlan::nseg)
+      .def_readonly("ngroups", &LambPlan::ngroups);
+  m.def("lamb_plan", &lamb_plan, py::arg("master"), py::arg("chunks"), py::arg("seg_first_chunk"));
+  m.def("lamb_moments", &lamb_moments);
+  m.def("lamb_ratio", &lamb_ratio);
+  m.def("lamb_apply", &lamb_apply);
+  m.def("lamb_step", &lamb_step);
   m.def("cast_f32_bf16", &cast_f32_bf16);
   m.def("cast_bf16_f32", &cast_bf16_f32);
   m.def("rccl_unique_id", []() { return py::bytes(hq_rccl_unique_id()); });

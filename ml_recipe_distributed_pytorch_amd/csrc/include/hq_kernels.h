@@ -165,6 +165,30 @@ void hq_adamw(float* master, uint16_t* compute, const float* grad, float* m, flo
 void hq_adamod(float* master, uint16_t* compute, const float* grad, float* m, float* v, float* n, const HqOptChunk* chunks,
                int nchunks, HqOptGroups groups, HqBeta beta1, HqBeta beta2, HqBeta beta3, float eps, float bias_corr,
                const float* clip_coef, hipStream_t s);
+// LAMB (Adam + per-segment trust ratio ‖w‖/‖update‖): three launches over the same chunk table.
+//   u = (m·bc1) / (sqrt(v·bc2) + eps) + wd·p        eps AFTER the bias correction of v, decay inside u
+//   hq_lamb_moments : m, v updated; partials[c] = (Σp², Σu²) of chunk c, p BEFORE the update
+//   hq_lamb_ratio   : norms[s] = (W_s, U_s, r_s), r_s = W_s/U_s if adapt[group] and W_s > 0 and U_s > 0, else 1;
+//                     seg_first_chunk: int32 [nseg+1], the chunks of segment s are [first[s], first[s+1])
+//   hq_lamb_apply   : p -= (lr·r_s)·u with u recomputed from the new m, v; bf16 copy of p; chunk_seg: int32 [nchunks]
+// HqOptGroups is shared with adamw / adamod and keeps its layout; LAMB carries its own table.
+struct HqLambGroups {
+  float lr[kOptMaxGroups];
+  float wd[kOptMaxGroups];
+  int32_t adapt[kOptMaxGroups];
+};
+struct HqLambArgs {
+  float beta1, beta2, om1, om2, eps, bc1, bc2;   // om = HqBeta::one_minus; bc = 1/(1 − β^t) or 1, rounded once
+  HqLambArgs(HqBeta b1, HqBeta b2, float eps_, float bc1_, float bc2_)
+      : beta1(b1.beta), beta2(b2.beta), om1(b1.one_minus), om2(b2.one_minus), eps(eps_), bc1(bc1_), bc2(bc2_) {}
+};
+void hq_lamb_moments(const float* master, const float* grad, float* m, float* v, const HqOptChunk* chunks, int nchunks,
+                     HqLambGroups groups, HqLambArgs a, const float* clip_coef, float* partials, hipStream_t s);
+void hq_lamb_ratio(const float* partials, const HqOptChunk* chunks, const int32_t* seg_first_chunk, int nseg,
+                   HqLambGroups groups, float* norms, hipStream_t s);
+void hq_lamb_apply(float* master, uint16_t* compute, const float* m, const float* v, const HqOptChunk* chunks,
+                   const int32_t* chunk_seg, int nchunks, HqLambGroups groups, HqLambArgs a, const float* norms,
+                   hipStream_t s);
 void hq_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, float scale, hipStream_t s);
 void hq_cast_bf16_f32(const uint16_t* src, float* dst, int64_t n, float scale, hipStream_t s);
 

@@ -7,6 +7,8 @@
 //   hq_adamw / hq_adamod: one block per ≤8192-element chunk of a parameter segment; reads the
 //                         clip coefficient from device memory (no host sync), updates m, v (, n),
 //                         the fp32 master and writes the bf16 working copy in the same pass.
+//   hq_lamb_moments / _ratio / _apply : LAMB over the same chunk table — moments + per-chunk (Σp², Σu²), a fixed-order
+//                         per-segment fold to the trust ratio, then the update and the bf16 copy (no atomics)
 // HF AdamW semantics (reference init.py:137, correct_bias=False): decay applied AFTER the update.
 // AdaMod semantics (reference modules/model/trainer/optim.py:76-98): decay BEFORE the update.
 #include "hq_common.h"
@@ -195,6 +197,174 @@ __global__ __launch_bounds__(256) void adamod_kernel(float* __restrict__ master,
   }
 }
 
+// ------------------------------------------------------------------------------------------------------- LAMB
+// Adam with a per-segment trust ratio, three launches over the chunk table (hq_kernels.h has the contract).
+// u is never stored: lamb_moments_kernel folds it into Σu², lamb_apply_kernel recomputes it from the new m, v
+// through the same lamb_update, so both passes see the same number (the one contractable a·b + c is an explicit fmaf).
+__device__ __forceinline__ float lamb_update(float p, float m, float v, float wd, const HqLambArgs& a) {
+  return fmaf(wd, p, (m * a.bc1) / (sqrtf(v * a.bc2) + a.eps));
+}
+
+__device__ __forceinline__ void lamb_moments_elem(float p, float& m, float& v, float g, float wd, const HqLambArgs& a,
+                                                  float& sp, float& su) {
+  m = a.beta1 * m + a.om1 * g;
+  v = a.beta2 * v + a.om2 * g * g;
+  const float u = lamb_update(p, m, v, wd, a);
+  sp = fmaf(p, p, sp);
+  su = fmaf(u, u, su);
+}
+
+// Summation order of the two partials of a chunk (a function of the chunk's start and numel only, never of the grid):
+//   float4 path : thread t owns the float4 with index t, t + 256, t + 512, … of the chunk and adds their elements in
+//                 ascending index order (x, y, z, w of each) into ONE accumulator per sum by fmaf(e, e, acc) — the
+//                 two-quartet loop and its remainder loop visit the same indices in the same order; the numel % 4 tail
+//                 element 4·n4 + t (t < 3) comes last.  At most 8 float4 + 0 tail or 7 float4 + 1 tail: <= 32 additions.
+//   scalar path : thread t owns elements t, t + 256, … in ascending order: <= 32 additions.
+//   block fold  : hq_wave_sum (xor butterfly 32, 16, 8, 4, 2, 1: 6 additions), then ((w0 + w1) + w2) + w3 over the
+//                 four waves: 3 additions.
+// Longest addition chain of a chunk partial: 32 + 6 + 3 = 41.
+__global__ __launch_bounds__(256) void lamb_moments_kernel(const float* __restrict__ master, const float* __restrict__ grad,
+                                                           float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
+                                                           const HqOptChunk* __restrict__ chunks, HqLambGroups groups,
+                                                           HqLambArgs a, const float* __restrict__ clip,
+                                                           float* __restrict__ partials) {
+  __shared__ float red[8];
+  const HqOptChunk c = chunks[blockIdx.x];
+  const float wd = groups.wd[c.group];
+  const float cc = clip ? clip[0] : 1.f;
+  const int64_t s0 = c.start;
+  float sp = 0.f, su = 0.f;
+  if ((s0 & 3) == 0) {
+    const int n4 = c.numel / 4;
+    auto step4 = [&](int64_t o, const float4& p, float4& m, float4& v, const float4& g) {
+      lamb_moments_elem(p.x, m.x, v.x, g.x * cc, wd, a, sp, su);
+      lamb_moments_elem(p.y, m.y, v.y, g.y * cc, wd, a, sp, su);
+      lamb_moments_elem(p.z, m.z, v.z, g.z * cc, wd, a, sp, su);
+      lamb_moments_elem(p.w, m.w, v.w, g.w * cc, wd, a, sp, su);
+      st_nt4(exp_avg + o, m);
+      st_nt4(exp_avg_sq + o, v);
+    };
+    int i = threadIdx.x;
+    for (; i + 256 < n4; i += 512) {   // as adamw_kernel: two quartets per stream in flight
+      const int64_t o0 = s0 + 4 * (int64_t)i, o1 = o0 + 4 * 256;
+      const float4 p0 = ld_nt4(master + o0), p1 = ld_nt4(master + o1);
+      float4 m0 = ld_nt4(exp_avg + o0), m1 = ld_nt4(exp_avg + o1);
+      float4 v0 = ld_nt4(exp_avg_sq + o0), v1 = ld_nt4(exp_avg_sq + o1);
+      const float4 g0 = ld_nt4(grad + o0), g1 = ld_nt4(grad + o1);
+      step4(o0, p0, m0, v0, g0);
+      step4(o1, p1, m1, v1, g1);
+    }
+    for (; i < n4; i += 256) {
+      const int64_t o = s0 + 4 * (int64_t)i;
+      const float4 p = *reinterpret_cast<const float4*>(master + o);
+      float4 m = *reinterpret_cast<float4*>(exp_avg + o);
+      float4 v = *reinterpret_cast<float4*>(exp_avg_sq + o);
+      const float4 g = *reinterpret_cast<const float4*>(grad + o);
+      step4(o, p, m, v, g);
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < c.numel; i += 256) {
+      const int64_t o = s0 + i;
+      lamb_moments_elem(master[o], exp_avg[o], exp_avg_sq[o], grad[o] * cc, wd, a, sp, su);
+    }
+  } else {
+    for (int i = threadIdx.x; i < c.numel; i += 256) {
+      const int64_t o = s0 + i;
+      lamb_moments_elem(master[o], exp_avg[o], exp_avg_sq[o], grad[o] * cc, wd, a, sp, su);
+    }
+  }
+  sp = hq_wave_sum(sp);
+  su = hq_wave_sum(su);
+  if ((threadIdx.x & 63) == 0) {
+    red[threadIdx.x >> 6] = sp;
+    red[4 + (threadIdx.x >> 6)] = su;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partials[2 * (int64_t)blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    partials[2 * (int64_t)blockIdx.x + 1] = ((red[4] + red[5]) + red[6]) + red[7];
+  }
+}
+
+// One wave per segment (four segments per block).  Lane l adds the partials of chunks first + l, first + l + 64, … of
+// its segment in ascending order into one accumulator per sum (ceil(nchunks_s / 64) additions, the first onto 0), then
+// hq_wave_sum (6 additions): the order depends on the segment's chunk count only.
+// norms[s] = (W_s, U_s, r_s).
+__global__ __launch_bounds__(256) void lamb_ratio_kernel(const float* __restrict__ partials,
+                                                         const HqOptChunk* __restrict__ chunks,
+                                                         const int32_t* __restrict__ seg_first_chunk, int nseg,
+                                                         HqLambGroups groups, float* __restrict__ norms) {
+  const int seg = blockIdx.x * 4 + (threadIdx.x >> 6);   // wave-uniform
+  if (seg >= nseg) return;
+  const int lane = threadIdx.x & 63;
+  const int c0 = seg_first_chunk[seg], c1 = seg_first_chunk[seg + 1];
+  float sp = 0.f, su = 0.f;
+  for (int c = c0 + lane; c < c1; c += 64) {
+    sp += partials[2 * (int64_t)c];
+    su += partials[2 * (int64_t)c + 1];
+  }
+  sp = hq_wave_sum(sp);
+  su = hq_wave_sum(su);
+  if (lane == 0) {
+    const float W = sqrtf(sp), U = sqrtf(su);
+    const bool adapt = groups.adapt[chunks[c0].group] != 0;
+    norms[3 * (int64_t)seg] = W;
+    norms[3 * (int64_t)seg + 1] = U;
+    norms[3 * (int64_t)seg + 2] = (adapt && W > 0.f && U > 0.f) ? W / U : 1.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void lamb_apply_kernel(float* __restrict__ master, uint16_t* __restrict__ compute,
+                                                         const float* __restrict__ exp_avg,
+                                                         const float* __restrict__ exp_avg_sq,
+                                                         const HqOptChunk* __restrict__ chunks,
+                                                         const int32_t* __restrict__ chunk_seg, HqLambGroups groups,
+                                                         HqLambArgs a, const float* __restrict__ norms) {
+  const HqOptChunk c = chunks[blockIdx.x];
+  const float wd = groups.wd[c.group];
+  const float nlr = -(groups.lr[c.group] * norms[3 * (int64_t)chunk_seg[blockIdx.x] + 2]);
+  const int64_t s0 = c.start;
+  auto elem = [&](float p, float m, float v) { return fmaf(nlr, lamb_update(p, m, v, wd, a), p); };
+  if ((s0 & 3) == 0) {
+    const int n4 = c.numel / 4;
+    auto step4 = [&](int64_t o, float4 p, const float4& m, const float4& v) {
+      p.x = elem(p.x, m.x, v.x);
+      p.y = elem(p.y, m.y, v.y);
+      p.z = elem(p.z, m.z, v.z);
+      p.w = elem(p.w, m.w, v.w);
+      st_nt4(master + o, p);
+      if (compute) {
+        const float pf[4] = {p.x, p.y, p.z, p.w};
+        st_nt2(compute + o, hq_pack4(pf));
+      }
+    };
+    int i = threadIdx.x;
+    for (; i + 256 < n4; i += 512) {
+      const int64_t o0 = s0 + 4 * (int64_t)i, o1 = o0 + 4 * 256;
+      const float4 p0 = ld_nt4(master + o0), p1 = ld_nt4(master + o1);
+      const float4 m0 = ld_nt4(exp_avg + o0), m1 = ld_nt4(exp_avg + o1);
+      const float4 v0 = ld_nt4(exp_avg_sq + o0), v1 = ld_nt4(exp_avg_sq + o1);
+      step4(o0, p0, m0, v0);
+      step4(o1, p1, m1, v1);
+    }
+    for (; i < n4; i += 256) {
+      const int64_t o = s0 + 4 * (int64_t)i;
+      step4(o, *reinterpret_cast<const float4*>(master + o), *reinterpret_cast<const float4*>(exp_avg + o),
+            *reinterpret_cast<const float4*>(exp_avg_sq + o));
+    }
+    for (int i = n4 * 4 + threadIdx.x; i < c.numel; i += 256) {
+      const int64_t o = s0 + i;
+      master[o] = elem(master[o], exp_avg[o], exp_avg_sq[o]);
+      if (compute) compute[o] = hq_f2bf(master[o]);
+    }
+  } else {
+    for (int i = threadIdx.x; i < c.numel; i += 256) {
+      const int64_t o = s0 + i;
+      master[o] = elem(master[o], exp_avg[o], exp_avg_sq[o]);
+      if (compute) compute[o] = hq_f2bf(master[o]);
+    }
+  }
+}
+
 __global__ __launch_bounds__(256) void cast_f32_bf16_kernel(const float* __restrict__ src, uint16_t* __restrict__ dst,
                                                             int64_t n, float scale) {
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -276,6 +446,25 @@ void hq_adamod(float* master, uint16_t* compute, const float* grad, float* m, fl
   AdaModArgs a{beta1.beta, beta2.beta, beta3.beta, beta1.one_minus, beta2.one_minus, beta3.one_minus, eps, bias_corr};
   hipLaunchKernelGGL(adamod_kernel, dim3(nchunks), dim3(256), 0, s, master, compute, grad, m, v, n, chunks, groups, a,
                      clip_coef);
+}
+
+void hq_lamb_moments(const float* master, const float* grad, float* m, float* v, const HqOptChunk* chunks, int nchunks,
+                     HqLambGroups groups, HqLambArgs a, const float* clip_coef, float* partials, hipStream_t s) {
+  hipLaunchKernelGGL(lamb_moments_kernel, dim3(nchunks), dim3(256), 0, s, master, grad, m, v, chunks, groups, a, clip_coef,
+                     partials);
+}
+
+void hq_lamb_ratio(const float* partials, const HqOptChunk* chunks, const int32_t* seg_first_chunk, int nseg,
+                   HqLambGroups groups, float* norms, hipStream_t s) {
+  hipLaunchKernelGGL(lamb_ratio_kernel, dim3((nseg + 3) / 4), dim3(256), 0, s, partials, chunks, seg_first_chunk, nseg,
+                     groups, norms);
+}
+
+void hq_lamb_apply(float* master, uint16_t* compute, const float* m, const float* v, const HqOptChunk* chunks,
+                   const int32_t* chunk_seg, int nchunks, HqLambGroups groups, HqLambArgs a, const float* norms,
+                   hipStream_t s) {
+  hipLaunchKernelGGL(lamb_apply_kernel, dim3(nchunks), dim3(256), 0, s, master, compute, m, v, chunks, chunk_seg, groups, a,
+                     norms);
 }
 
 void hq_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, float scale, hipStream_t s) {

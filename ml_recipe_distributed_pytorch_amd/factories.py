@@ -23,7 +23,7 @@ from .data.items import LABELS, LABELS2ID
 from .models.bert import BertForQuestionAnswering, load_pretrained
 from .models.config import get_config
 from .models.losses import build_loss
-from .train.optim import FusedAdaMod, FusedAdamW
+from .train.optim import FusedAdaMod, FusedAdamW, FusedLamb
 from .train.trainer import optimizer_groups
 
 logger = logging.getLogger(__name__)
@@ -120,9 +120,13 @@ def _optimized_parameters(params, model):
 def init_optimizer(params, model):
     modules, named = _optimized_parameters(params, model)
     groups = optimizer_groups(named, params.weight_decay)
+    if params.optimizer == "lamb":
+        groups[1]["adapt"] = False   # biases / LayerNorm: no layer adaptation (marked before empty groups are dropped)
     groups = [g for g in groups if g["params"]]
     if params.optimizer == "adam":
         opt = FusedAdamW(groups, model.store, lr=params.lr, eps=1e-6, correct_bias=False, zero_grad_fn=model.zero_grad)
+    elif params.optimizer == "lamb":
+        opt = FusedLamb(groups, model.store, lr=params.lr, eps=1e-6, zero_grad_fn=model.zero_grad)
     else:
         opt = FusedAdaMod(groups, model.store, lr=params.lr, zero_grad_fn=model.zero_grad)
     logger.info(f"Used optimizer: {type(opt).__name__}.")

@@ -284,6 +284,40 @@ def adamod_step(master, compute, grad, exp_avg, exp_avg_sq, exp_avg_lr, segments
             compute[start:start + numel].copy_(master[start:start + numel])
 
 
+def lamb_step(master, compute, grad, exp_avg, exp_avg_sq, segments, *, lr, beta1, beta2, eps,
+              clip_coef: Optional[Tensor], correct_bias: bool, step: int, adapt: bool = True) -> Tensor:
+    """LAMB (You et al. 2020, Algorithm 2) over flat arena segments; one segment = one parameter = one "layer".
+
+        u = (m·bc1) / (sqrt(v·bc2) + eps) + wd·p      eps AFTER the bias correction of v, decay inside u
+        r = ‖p‖ / ‖u‖ over the segment (p before the update) if adapt and both norms > 0, else 1
+        p = p − (lr·r)·u
+
+    ``segments``: list of (start, numel, weight_decay).  Returns ``[len(segments), 3]`` = (‖p‖, ‖u‖, r) per segment.
+    """
+    g = grad if clip_coef is None else grad * clip_coef
+    bc1 = 1.0 / (1.0 - beta1 ** step) if correct_bias else 1.0
+    bc2 = 1.0 / (1.0 - beta2 ** step) if correct_bias else 1.0
+    norms = torch.ones(len(segments), 3, dtype=master.dtype, device=master.device)
+    lr_t = torch.tensor(lr, dtype=master.dtype, device=master.device)
+    for i, (start, numel, wd) in enumerate(segments):
+        sl = slice(start, start + numel)
+        gg = g[sl]
+        m, v, p = exp_avg[sl], exp_avg_sq[sl], master[sl]
+        m.mul_(beta1).add_(gg, alpha=1.0 - beta1)
+        v.mul_(beta2).addcmul_(gg, gg, value=1.0 - beta2)
+        u = (m * bc1).div_((v * bc2).sqrt_().add_(eps))
+        if wd != 0.0:
+            u.add_(p, alpha=wd)
+        W, U = p.square().sum().sqrt(), u.square().sum().sqrt()
+        r = W / U if (adapt and bool(W > 0) and bool(U > 0)) else torch.ones_like(W)
+        norms[i, 0], norms[i, 1], norms[i, 2] = W, U, r
+        p.sub_(u.mul_(lr_t * r))
+    if compute is not None and compute.data_ptr() != master.data_ptr():
+        for start, numel, _ in segments:
+            compute[start:start + numel].copy_(master[start:start + numel])
+    return norms
+
+
 # ------------------------------------------------------------------------------------ inference decode
 def qa_decode(start, end, cls, start_reg, end_reg, lo, hi, max_answer_len: int) -> Tensor:
     """Joint valid-span decode, the definition ``csrc/kernels/decode.hip`` implements bit for bit.

@@ -13,7 +13,8 @@ per layer and sample (L tokens, bf16 = 2 B):
     attention dropout keep-bits ............ nh·L²/8
 plus the backward's transient working set of one layer (dpre, dqkv, ~6 [L, H] gradients, split-K slabs),
 the embedding / heads activations and the parameter state (fp32 master + bf16 compute copy + bf16 Wᵀ
-copies of the encoder weights + fp32 grad + AdamW m, v = 22 B per parameter).
+copies of the encoder weights + fp32 grad + AdamW m, v = 22 B per parameter).  ``--optimizer lamb`` has the same
+state as AdamW (m, v; its norm partials and ratios are a few KB), so the 22 B hold for it unchanged.
 
 ``tests/test_memory_model.py`` pins the formula on CPU; ``tests/test_model_gpu.py`` checks it against
 ``torch.cuda.max_memory_allocated`` of real steps (within 15 %).

@@ -6,8 +6,10 @@
 * ``FusedAdaMod`` = reference ``modules/model/trainer/optim.py:8-100`` (decay before the update,
   beta3 EMA bound on the per-element step size), rewritten without the removed ``add_(scalar, t)``
   overloads (D17).
+* ``FusedLamb`` = LAMB (You et al. 2020, Algorithm 2) for large-batch runs: AdamW's state, three launches per
+  step (moments + per-chunk norm partials, per-parameter trust ratio, update); not in the reference.
 
-Both are ``torch.optim.Optimizer`` subclasses (so ``LambdaLR`` and ``state_dict()`` work and the
+All are ``torch.optim.Optimizer`` subclasses (so ``LambdaLR`` and ``state_dict()`` work and the
 checkpoint layout matches the reference: per-param ``step/exp_avg/exp_avg_sq``), but their state
 tensors are *views* into flat arenas and ``step()`` is ONE kernel on GPU (``_hq_kernels.adamw``)
 that also reads the on-device clip coefficient and refreshes the bf16 working copy.  On CPU the
@@ -203,6 +205,81 @@ class FusedAdaMod(_ArenaOptimizer):
                                 eps=g["eps"], clip_coef=clip_coef, step=step)
         st.mark_clean()
         return loss
+
+
+class FusedLamb(_ArenaOptimizer):
+    """LAMB: Adam moments, then per parameter (one arena segment = one "layer") the trust ratio
+    ``r = ‖p‖ / ‖u‖`` scales the step (``ops.reference.lamb_step`` is the definition).  ``adapt`` is a per-group
+    key: a group with ``adapt=False`` (biases, LayerNorm) takes the plain Adam-with-decay step, ``r = 1``.
+
+    GPU: three launches over the chunk table (``lamb_moments`` → ``lamb_ratio`` → ``lamb_apply``), every reduction
+    in a fixed order, no atomics; the gradient arena is only read.  The state is AdamW's (``exp_avg``,
+    ``exp_avg_sq``), so the checkpoint layout is the same."""
+    state_names = ("exp_avg", "exp_avg_sq")
+
+    def __init__(self, params, store: ParamStore, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-6,
+                 weight_decay: float = 0.0, correct_bias: bool = True, adapt: bool = True, zero_grad_fn=None):
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, correct_bias=correct_bias, adapt=adapt)
+        super().__init__(params, defaults, store, zero_grad_fn)
+        for name in self.state_names:
+            self._arena(name)
+        self._plan = None
+        self._partials: Optional[torch.Tensor] = None
+        self._norms: Optional[torch.Tensor] = None      # [nseg, 3] = (W, U, r) of the last step, on the arena's device
+
+    def _lamb_plan(self):
+        """Chunk table, ``seg_first_chunk`` and the per-chunk segment index, checked and uploaded once per device."""
+        master = self.store.master
+        if self._plan is None or self._plan.chunks.device != master.device:
+            rows, first = [], [0]
+            for s, n, g in self._segments:
+                for off in range(0, n, CHUNK):
+                    rows.append([s + off, min(CHUNK, n - off) | (g << 32)])
+                first.append(len(rows))
+            self._plan = kernels().lamb_plan(master, torch.tensor(rows, dtype=torch.int64),
+                                             torch.tensor(first, dtype=torch.int32))
+            self._partials = torch.zeros(len(rows), 2, dtype=torch.float32, device=master.device)
+            self._norms = torch.ones(len(self._segments), 3, dtype=torch.float32, device=master.device)
+        return self._plan
+
+    @torch.no_grad()
+    def step(self, closure=None, clip_coef: Optional[torch.Tensor] = None):
+        loss = closure() if closure is not None else None
+        self._sync_device()
+        self._bump_steps()
+        step = self._step_count()
+        g0 = self.param_groups[0]
+        b1, b2 = g0["betas"]
+        st = self.store
+        if st.master.is_cuda:
+            bc1 = 1.0 / (1.0 - b1 ** step) if g0["correct_bias"] else 1.0
+            bc2 = 1.0 / (1.0 - b2 ** step) if g0["correct_bias"] else 1.0
+            compute = st.compute if st.compute.data_ptr() != st.master.data_ptr() else None
+            plan = self._lamb_plan()
+            kernels().lamb_step(plan, st.master, compute, st.grad, self._arenas["exp_avg"], self._arenas["exp_avg_sq"],
+                                [g["lr"] for g in self.param_groups], [g["weight_decay"] for g in self.param_groups],
+                                [bool(g["adapt"]) for g in self.param_groups], b1, b2, g0["eps"], bc1, bc2, clip_coef,
+                                self._partials, self._norms)
+        else:
+            if self._norms is None or self._norms.is_cuda:
+                self._norms = torch.ones(len(self._segments), 3, dtype=torch.float32)
+            for gi, g in enumerate(self.param_groups):
+                rows = [i for i, (_, _, gg) in enumerate(self._segments) if gg == gi]
+                segs = [self._segments[i][:2] + (g["weight_decay"],) for i in rows]
+                self._norms[rows] = ref.lamb_step(st.master, None, st.grad, self._arenas["exp_avg"],
+                                                  self._arenas["exp_avg_sq"], segs, lr=g["lr"], beta1=b1, beta2=b2,
+                                                  eps=g["eps"], clip_coef=clip_coef, correct_bias=g["correct_bias"],
+                                                  step=step, adapt=bool(g["adapt"])).float()
+        st.mark_clean()
+        return loss
+
+    def trust_ratios(self) -> Dict[str, Tuple[float, float, float]]:
+        """``{parameter name: (‖p‖, ‖u‖, r)}`` of the last step; the one device→host copy happens here."""
+        if self._norms is None:
+            raise RuntimeError("trust_ratios() before the first step()")
+        names = {start: name for start, _, name in self.store.segments()}
+        host = self._norms.cpu().tolist()
+        return {names[s]: tuple(row) for (s, _, _), row in zip(self._segments, host)}
 
 
 def grad_norm_and_clip(store: ParamStore, max_norm: float, partials: Optional[torch.Tensor] = None):

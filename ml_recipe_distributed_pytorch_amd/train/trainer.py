@@ -40,7 +40,7 @@ from .callbacks import TestCallback
 from .amp import apex_to_precision, resolve_precision  # noqa: F401  (apex_to_precision re-exported)
 from .engine import TrainEngine, prefetch_to_device, to_device
 from .meters import AverageMeter
-from .optim import get_linear_schedule_with_warmup
+from .optim import FusedLamb, get_linear_schedule_with_warmup
 
 logger = logging.getLogger(__name__)
 
@@ -343,6 +343,10 @@ class Trainer:
                     for k in ("perf/samples_per_sec", "perf/step_ms"):
                         if k in avg:
                             self.writer.add_scalar(k, avg[k], global_step=self.global_step)
+                    if isinstance(self.optimizer, FusedLamb):   # one host copy of [params, 3] per log step
+                        r = sorted(v[2] for v in self.optimizer.trust_ratios().values())
+                        for k, v in (("min", r[0]), ("median", r[len(r) // 2]), ("max", r[-1])):
+                            self.writer.add_scalar(f"opt/trust_ratio_{k}", v, global_step=self.global_step)
                     if self.profile:
                         for k, v in res.timings.items():
                             self.writer.add_scalar(f"perf/{k}", v, global_step=self.global_step)

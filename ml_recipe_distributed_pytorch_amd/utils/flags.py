@@ -160,7 +160,8 @@ def get_trainer_parser() -> ArgumentParser:
     parser.add_argument("--finetune_position_reg", action="store_true", help="Finetune regression head.")
     parser.add_argument("--finetune_class", action="store_true", help="Finetune doc label classification head.")
     parser.add_argument("--bpe_dropout", type=cast2(float), default=None, help="Use BPE dropout.")
-    parser.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamod"], help="Optimizer name.")
+    parser.add_argument("--optimizer", type=str, default="adam", choices=["adam", "adamod", "lamb"],
+                        help="Optimizer name (lamb: layer-wise trust ratio, for large global batches).")
     parser.add_argument("--train_label_weights", action="store_true", help="Use label weights in CE loss.")
     parser.add_argument("--train_sampler_weights", action="store_true", help="Use oversampling.")
     parser.add_argument("--log_file", type=str, default=None,
