@@ -218,22 +218,22 @@ Tensor gemm_nt(Tensor A, Tensor B, int64_t epi, c10::optional<Tensor> bias, c10:
   Tensor C = has(out) ? *out : at::empty({M, N}, A.options());
   check(C, BF16, "out");
   TORCH_CHECK(C.size(0) == M && C.size(1) == N, "gemm_nt: out shape");
-  if (epi == HQ_EPI_BIAS || epi == HQ_EPI_GELU || epi == HQ_EPI_GELUD) {
+  if (hq_epi_has_bias((int)epi) && epi != HQ_EPI_BDR) {   // (BDR's bias: checked above)
     TORCH_CHECK(has(bias), "gemm_nt: bias required");
     check(*bias, F32, "bias");
     TORCH_CHECK(bias->numel() == N, "gemm_nt: bias length");
   }
-  if (epi == HQ_EPI_GELU || epi == HQ_EPI_DGELU || epi == HQ_EPI_GELUD || epi == HQ_EPI_DMUL) {
+  if (hq_epi_writes_p((int)epi) || hq_epi_col_partials((int)epi)) {   // P written, or read as the operand
     TORCH_CHECK(has(pre), "gemm_nt: pre required");
     check(*pre, BF16, "pre");
     TORCH_CHECK(pre->size(0) == M && pre->size(1) == N, "gemm_nt: pre shape");
   }
-  if (epi == HQ_EPI_RESID || epi == HQ_EPI_BDR) {
+  if (hq_epi_reads_aux((int)epi) && !hq_epi_col_partials((int)epi)) {   // the operand is R
     TORCH_CHECK(has(resid), "gemm_nt: resid required");
     check(*resid, BF16, "resid");
     TORCH_CHECK(resid->size(0) == M && resid->size(1) == N, "gemm_nt: resid shape");
   }
-  if (epi == HQ_EPI_DGELU || epi == HQ_EPI_DMUL) {
+  if (hq_epi_col_partials((int)epi)) {
     TORCH_CHECK(has(part), "gemm_nt: part required");
     check(*part, F32, "part");
     TORCH_CHECK(part->numel() == (int64_t)hq_gemm_nt_part_rows((int)M, (int)N, (int)K) * N,

@@ -106,6 +106,15 @@ __device__ __forceinline__ float hq_wave_max(float v) {
   return v;
 }
 
+// ------------------------------------------------------------------------------ tile order
+// XCD-aware bijective remap of the linear workgroup id `bid` of an `nwg`-workgroup grid: consecutive ids go round
+// the 8 XCDs, so XCD x = bid & 7 gets the ids x, x + 8, …; the result gives each XCD a contiguous range of work
+// items in the order it meets them, so that the items that share an operand panel share that XCD's L2.
+__device__ __forceinline__ int hq_xcd_tile(int bid, int nwg) {
+  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
 // ------------------------------------------------------------------------------ dropout RNG
 // key = fmix32(seed ^ opid*0x9E3779B9) is computed on the host (hq_op_key) once per op.
 __host__ __device__ __forceinline__ uint32_t hq_fmix32(uint32_t h) {

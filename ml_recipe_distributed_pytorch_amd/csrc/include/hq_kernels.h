@@ -5,6 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 #include <algorithm>
+#include <initializer_list>
 #include <type_traits>
 
 // --precision fp8: 8-bit linear code of gelu'(pre) between the FFN1 forward and the FFN2 dgrad (hq_common.h,
@@ -13,6 +14,15 @@ constexpr float kHqGdLo = -0.12890625f;
 constexpr float kHqGdStep = 1.2578125f / 255.f;
 constexpr float kHqGdInv = 255.f / 1.2578125f;       // encode: q = rne(fma(g, kHqGdInv, kHqGdOff)), clamp 0…255
 constexpr float kHqGdOff = -kHqGdLo * kHqGdInv;
+
+// Raise the dynamic-LDS limit of `kernels` to `bytes`; the initialiser of a call site's function-local static, so
+// it runs once per site:  [[maybe_unused]] static const bool once = hq_raise_lds_limit({(const void*)kern}, lds);
+inline bool hq_raise_lds_limit(std::initializer_list<const void*> kernels, size_t bytes) {
+  bool ok = true;
+  for (const void* k : kernels)
+    ok &= hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+  return ok;
+}
 
 struct HqOuts {  // up to 4 fp32 column-sum destinations (null = skip), passed by value
   float* p[4];
@@ -195,6 +205,16 @@ void hq_cast_bf16_f32(const uint16_t* src, float* dst, int64_t n, float scale, h
 // ------------------------------------------------------------------ MFMA GEMM (gemm.hip)
 enum { HQ_EPI_NONE = 0, HQ_EPI_BIAS = 1, HQ_EPI_GELU = 2, HQ_EPI_DGELU = 3, HQ_EPI_RESID = 4, HQ_EPI_GELUD = 5, HQ_EPI_DMUL = 6,
        HQ_EPI_BDR = 7 };
+// what an epilogue touches beside C (host and device): the fp32 bias; a second bf16 [M,N] operand (DGELU / DMUL: P,
+// RESID / BDR: R); per-block column sums into part (exactly the epilogues whose operand is P); a P output
+constexpr bool hq_epi_has_bias(int epi) {
+  return epi == HQ_EPI_BIAS || epi == HQ_EPI_GELU || epi == HQ_EPI_GELUD || epi == HQ_EPI_BDR;
+}
+constexpr bool hq_epi_reads_aux(int epi) {
+  return epi == HQ_EPI_DGELU || epi == HQ_EPI_DMUL || epi == HQ_EPI_RESID || epi == HQ_EPI_BDR;
+}
+constexpr bool hq_epi_col_partials(int epi) { return epi == HQ_EPI_DGELU || epi == HQ_EPI_DMUL; }
+constexpr bool hq_epi_writes_p(int epi) { return epi == HQ_EPI_GELU || epi == HQ_EPI_GELUD; }
 // kernel family for this shape: 256 / 128 = the 256-row kernels with that block width, 1 = the 128²-tile
 // kernel (M tails, low-fill grids), 0 = unsupported (need N % 128 == 0, K % 64 == 0)
 int hq_gemm_nt_supported(int M, int N, int K);

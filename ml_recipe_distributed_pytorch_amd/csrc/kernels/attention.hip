@@ -471,8 +471,7 @@ __global__ __launch_bounds__(RW * 64, 4) void attn_fwd_ring_kernel(const uint16_
   uint2* sA = reinterpret_cast<uint2*>(ring + RNS * 2 * RTILE);     // [Lp]: (pk(b_hi, b_lo), pk(1, 0))
   // XCD-aware block order (bijective): blocks b, b+8, … share an XCD; give each XCD a contiguous run of
   // (head, query-block) pairs with the query block fastest, so a head's blocks are co-resident on one L2
-  const int nblk = gridDim.x, ob = blockIdx.x, xcd = ob & 7, qq = nblk >> 3, rr = nblk & 7;
-  const int lin = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (ob >> 3);
+  const int nblk = gridDim.x, lin = hq_xcd_tile(blockIdx.x, nblk);
   const int bh = lin / n_qb, qb = lin - bh * n_qb;
   const int b = bh / nh, h = bh - b * nh;
   const int H = nh * D, ld = 3 * H;
@@ -774,8 +773,7 @@ __global__ __launch_bounds__(RW * 64, MODE == 0 && NT > 0 ? 4 : 3) void attn_bwd
   char* ring = reinterpret_cast<char*>(smem);                       // [RNS][K 4 KB | V 4 KB]
   uint32_t* sA = reinterpret_cast<uint32_t*>(ring + RNS * 2 * RTILE);  // [Lp] A' word 0 (b_hi,b_lo); 1-3 constant
   uint16_t* sM = reinterpret_cast<uint16_t*>(sA + Lp);              // [RW][n32][64] dropout words
-  const int nblk = gridDim.x, ob = blockIdx.x, xcd = ob & 7, qq = nblk >> 3, rr = nblk & 7;
-  const int lin = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (ob >> 3);
+  const int nblk = gridDim.x, lin = hq_xcd_tile(blockIdx.x, nblk);
   const int bh = lin / n_qb, qb = lin - bh * n_qb;
   const int b = bh / nh, h = bh - b * nh;
   const int H = nh * D, ld = 3 * H;
@@ -939,8 +937,7 @@ __global__ __launch_bounds__(RW * 64, 2) void attn_bwd_dkdv_ring_kernel(
   constexpr int SLOT = 2 * RTILE + 512 + 128 + RW * 128;
   static_assert(2 * SLOT >= RW * 4096, "dK/dV store staging: 4 KiB per wave in the two slots");
   const int Lp = NT > 0 ? NT * 32 : (L + 31) & ~31, n32 = Lp >> 5;
-  const int nblk = gridDim.x, ob = blockIdx.x, xcd = ob & 7, qq = nblk >> 3, rr = nblk & 7;
-  const int lin = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (ob >> 3);
+  const int nblk = gridDim.x, lin = hq_xcd_tile(blockIdx.x, nblk);
   const int bh = lin / n_kb, kbk = lin - bh * n_kb;
   const int b = bh / nh, h = bh - b * nh;
   const int H = nh * D, ld = 3 * H;
@@ -1220,9 +1217,7 @@ void hq_attn_fwd(const uint16_t* qkv, const float* key_bias, uint16_t* ctx, floa
     auto run = [&](auto cn) {
       constexpr int NT = decltype(cn)::value;
       auto launch1 = [&](auto kern) {
-        static bool attr =
-            (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess);
-        (void)attr;
+        [[maybe_unused]] static const bool once = hq_raise_lds_limit({(const void*)kern}, 64 * 1024);
         hipLaunchKernelGGL(kern, dim3(B * nh * n_qb), dim3(RW * 64), lds, s, qkv, key_bias, ctx, lse,
                            thr ? mbits : nullptr, L, nh, n_qb, scale * LOG2E, key, thr, hq_keep_scale(thr), force_slow,
                            ctx8, q8, part8, phase);
@@ -1272,9 +1267,7 @@ void hq_attn_bwd(const uint16_t* dctx, const uint16_t* qkv, const uint16_t* ctx,
     auto run = [&](auto cn) {
       constexpr int NT = decltype(cn)::value;
       auto launch = [&](auto kdq, auto kkv) {
-        static bool attr =
-            (hipFuncSetAttribute((const void*)kdq, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess);
-        (void)attr;
+        [[maybe_unused]] static const bool once = hq_raise_lds_limit({(const void*)kdq}, 64 * 1024);
         hipLaunchKernelGGL(kdq, dim3(B * nh * nb), dim3(RW * 64), lds_dq, s, qkv, dctx, ctx, lse, key_bias, bits, delta,
                            dqkv, L, nh, nb, scale * LOG2E, scale, ks, dqkv8, q8, part8, phase, bpart);
         hipLaunchKernelGGL(kkv, dim3(B * nh * nb), dim3(RW * 64), lds_kv, s, qkv, dctx, lse, delta, key_bias, bits, dqkv,

@@ -29,9 +29,11 @@
 //   so the tiles that share an A row-panel share that XCD's L2.
 #include <mutex>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "hq_common.h"
+#include "hq_gemm_epi.h"
 #include "hq_kernels.h"
 
 namespace {
@@ -46,9 +48,6 @@ typedef __attribute__((address_space(1))) void g_void;
 __device__ __forceinline__ f32x4_t mfma16(const bf16x8_t& a, const bf16x8_t& b, const f32x4_t& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
-
-__device__ __forceinline__ float gelu_erf(float x) { return hq_gelu(x); }
-__device__ __forceinline__ float gelu_grad(float x) { return hq_gelu_grad(x); }
 
 // Issue the LDS-DMA of one [ROWS × 64] bf16 panel (rows of 128 B) into lds (+ byte offset).
 // Each wave-instruction moves 8 rows (64 lanes × 16 B); this wave handles `n_instr` of them
@@ -92,11 +91,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt_kernel(const uint16_t* __
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
 
-  // ---- bijective XCD remap of the linear block id, then M-major tile order within an XCD
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int tile = hq_xcd_tile(blockIdx.x, gridDim.x);   // then M-major tile order within an XCD
   const int tiles_n = N / BN;
   const int tm = tile / tiles_n, tn = tile % tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -195,7 +190,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt_kernel(const uint16_t* __
   for (int j = 0; j < NJ; ++j) {
     const int nl = j * 16 + fq * 4;
     float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (EPI == HQ_EPI_BIAS || EPI == HQ_EPI_GELU || EPI == HQ_EPI_GELUD || EPI == HQ_EPI_BDR) bv = *reinterpret_cast<const float4*>(bias + n0 + wn * WN + nl);
+    if constexpr (hq_epi_has_bias(EPI)) bv = *reinterpret_cast<const float4*>(bias + n0 + wn * WN + nl);
 #pragma unroll
     for (int i = 0; i < MI; ++i) {
       float v[4] = {acc[i][j][0] + bv.x, acc[i][j][1] + bv.y, acc[i][j][2] + bv.z, acc[i][j][3] + bv.w};
@@ -207,8 +202,9 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt_kernel(const uint16_t* __
   constexpr int ROWS_PER_IT = 64 / SEGS;
   const int seg = lane % SEGS, rsub = lane / SEGS;
   const int mb = m0 + wm * 128, nb = n0 + wn * WN + seg * 8;
+  const uint16_t* aux_src = hq_epi_col_partials(EPI) ? P : R;
   float csum[8];
-  if constexpr (EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL) {
+  if constexpr (hq_epi_col_partials(EPI)) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) csum[e] = 0.f;
   }
@@ -217,51 +213,14 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt_kernel(const uint16_t* __
     const int row = it * ROWS_PER_IT + rsub;
     uint4 piece = *reinterpret_cast<const uint4*>(wreg + row * RS + seg * 16);
     const size_t goff = (size_t)(mb + row) * ldc + nb;
-    if constexpr (EPI == HQ_EPI_GELU) {
-      *reinterpret_cast<uint4*>(P + goff) = piece;   // pre-activation (bf16), kept for backward
-      float x[8];
-      hq_unpack8(piece, x);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = gelu_erf(x[e]);
-      piece = hq_pack8(x);
-    } else if constexpr (EPI == HQ_EPI_GELUD) {
-      float x[8], g[8];
-      hq_unpack8(piece, x);
-      hq_gelu_grad8(x, g);   // g = gelu'(x), x = gelu(x)
-      *reinterpret_cast<uint4*>(P + goff) = hq_pack8(g);
-      piece = hq_pack8(x);
-    } else if constexpr (EPI == HQ_EPI_DMUL) {
-      float d[8], gd[8];
-      hq_unpack8(piece, d);
-      hq_unpack8(*reinterpret_cast<const uint4*>(P + goff), gd);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { d[e] *= gd[e]; csum[e] += d[e]; }
-      piece = hq_pack8(d);
-    } else if constexpr (EPI == HQ_EPI_DGELU) {
-      float d[8], pr[8];
-      hq_unpack8(piece, d);
-      hq_unpack8(*reinterpret_cast<const uint4*>(P + goff), pr);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { d[e] *= gelu_grad(pr[e]); csum[e] += d[e]; }
-      piece = hq_pack8(d);
-    } else if constexpr (EPI == HQ_EPI_RESID) {
-      float d[8], rr[8];
-      hq_unpack8(piece, d);
-      hq_unpack8(*reinterpret_cast<const uint4*>(R + goff), rr);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) d[e] += rr[e];
-      piece = hq_pack8(d);
-    } else if constexpr (EPI == HQ_EPI_BDR) {
-      piece = hq_epi_bdr8(piece, *reinterpret_cast<const uint4*>(R + goff), (uint32_t)goff, dr, key);
-    }
+    hq_epi_piece<EPI>(piece, [&]() -> const uint4& { return *reinterpret_cast<const uint4*>(aux_src + goff); }, goff, dr,
+                      key, csum, [&](const uint4& p) { *reinterpret_cast<uint4*>(P + goff) = p; });
     *reinterpret_cast<uint4*>(C + goff) = piece;
   }
-  if constexpr (EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL) {
-    // column sums: lanes with equal `seg` hold the same 8 columns -> xor-reduce over rsub, then the
-    // two M-waves through LDS (after everyone is done with its staging region)
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      for (int o = SEGS; o < 64; o <<= 1) csum[e] += __shfl_xor(csum[e], o, 64);
+  if constexpr (hq_epi_col_partials(EPI)) {
+    // column sums: xor-reduce over rsub, then the two M-waves through LDS (after everyone is done with its
+    // staging region)
+    hq_epi_csum_reduce<SEGS>(csum);
     __syncthreads();
     float* red = reinterpret_cast<float*>(smem);  // [2][BN]
     if (rsub == 0) {
@@ -273,6 +232,9 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt_kernel(const uint16_t* __
   }
 }
 
+
+// vS split-K: only the epilogues without column partials, GELU or dropout (none / bias / resid)
+constexpr bool nts_can_split(int epi) { return !hq_epi_col_partials(epi) && !hq_epi_writes_p(epi) && epi != HQ_EPI_BDR; }
 
 // ============================================================================================
 // vS — 128×128 tiles for the shapes the 256-row kernels do not cover well: M % 256 != 0 (dynamically
@@ -302,9 +264,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nts_kernel(const uint16_t* __rest
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const int wm = wave >> 1, wn = wave & 1;
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int nwg = gridDim.x, id = hq_xcd_tile(blockIdx.x, nwg);
   const int tiles = nwg / ksplit;
   const int split = id / tiles, tile = id - split * tiles;
   const int tiles_n = N / SB;
@@ -312,8 +272,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nts_kernel(const uint16_t* __rest
   const int m0 = tm * SB, n0 = tn * SB;
   const int rows_a = min(SB, M - m0);
   const int nk = K / BK, kt0 = split * nk / ksplit, nt = (split + 1) * nk / ksplit - kt0;
-  HQ_DASSERT(rows_a > 0 && n0 + SB <= N && K % BK == 0 && nt > 0 && (ksplit == 1 || EPI == HQ_EPI_NONE ||
-             EPI == HQ_EPI_BIAS || EPI == HQ_EPI_RESID));
+  HQ_DASSERT(rows_a > 0 && n0 + SB <= N && K % BK == 0 && nt > 0 && (ksplit == 1 || nts_can_split(EPI)));
 
   const __amdgpu_buffer_rsrc_t ra =
       __builtin_amdgcn_make_buffer_rsrc((void*)(A + (size_t)m0 * lda), (short)0, rows_a * lda * 2, 0x00020000);
@@ -396,7 +355,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nts_kernel(const uint16_t* __rest
 
   // ---- epilogue: acc (+bias) -> bf16 in this wave's LDS region [64][64], then row-coalesced 16-B pieces
   char* wreg = smem + wave * 64 * RS;
-  constexpr bool kBias = EPI == HQ_EPI_BIAS || EPI == HQ_EPI_GELU || EPI == HQ_EPI_GELUD || EPI == HQ_EPI_BDR;
+  constexpr bool kBias = hq_epi_has_bias(EPI);
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int nl = j * 16 + fq * 4;
@@ -411,6 +370,7 @@ __global__ __launch_bounds__(256, 2) void gemm_nts_kernel(const uint16_t* __rest
   constexpr int SEGS = 8, ROWS_PER_IT = 64 / SEGS;
   const int seg = lane % SEGS, rsub = lane / SEGS;
   const int gcol = n0 + wn * 64 + seg * 8;
+  const uint16_t* aux_src = hq_epi_col_partials(EPI) ? P : R;
   float csum[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) csum[e] = 0.f;
@@ -421,49 +381,12 @@ __global__ __launch_bounds__(256, 2) void gemm_nts_kernel(const uint16_t* __rest
     if (grow >= M) continue;
     uint4 piece = *reinterpret_cast<const uint4*>(wreg + row * RS + seg * 16);
     const size_t goff = (size_t)grow * ldc + gcol;
-    if constexpr (EPI == HQ_EPI_GELU) {
-      *reinterpret_cast<uint4*>(P + goff) = piece;
-      float x[8];
-      hq_unpack8(piece, x);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = gelu_erf(x[e]);
-      piece = hq_pack8(x);
-    } else if constexpr (EPI == HQ_EPI_GELUD) {
-      float x[8], g[8];
-      hq_unpack8(piece, x);
-      hq_gelu_grad8(x, g);   // g = gelu'(x), x = gelu(x)
-      *reinterpret_cast<uint4*>(P + goff) = hq_pack8(g);
-      piece = hq_pack8(x);
-    } else if constexpr (EPI == HQ_EPI_DMUL) {
-      float d[8], gd[8];
-      hq_unpack8(piece, d);
-      hq_unpack8(*reinterpret_cast<const uint4*>(P + goff), gd);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { d[e] *= gd[e]; csum[e] += d[e]; }
-      piece = hq_pack8(d);
-    } else if constexpr (EPI == HQ_EPI_DGELU) {
-      float d[8], pr[8];
-      hq_unpack8(piece, d);
-      hq_unpack8(*reinterpret_cast<const uint4*>(P + goff), pr);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { d[e] *= gelu_grad(pr[e]); csum[e] += d[e]; }
-      piece = hq_pack8(d);
-    } else if constexpr (EPI == HQ_EPI_RESID) {
-      float d[8], rr[8];
-      hq_unpack8(piece, d);
-      hq_unpack8(*reinterpret_cast<const uint4*>(R + goff), rr);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) d[e] += rr[e];
-      piece = hq_pack8(d);
-    } else if constexpr (EPI == HQ_EPI_BDR) {
-      piece = hq_epi_bdr8(piece, *reinterpret_cast<const uint4*>(R + goff), (uint32_t)goff, dr, key);
-    }
+    hq_epi_piece<EPI>(piece, [&]() -> const uint4& { return *reinterpret_cast<const uint4*>(aux_src + goff); }, goff, dr,
+                      key, csum, [&](const uint4& p) { *reinterpret_cast<uint4*>(P + goff) = p; });
     *reinterpret_cast<uint4*>(C + goff) = piece;
   }
-  if constexpr (EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      for (int o = SEGS; o < 64; o <<= 1) csum[e] += __shfl_xor(csum[e], o, 64);
+  if constexpr (hq_epi_col_partials(EPI)) {
+    hq_epi_csum_reduce<SEGS>(csum);
     float* red = reinterpret_cast<float*>(smem + 4 * 64 * RS);  // [2][128], past the staging regions
     if (rsub == 0) {
 #pragma unroll
@@ -552,14 +475,13 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt2_kernel(const uint16_t* _
   // Half-tile tail (as v3's; production buffer-load form, ungrouped order only): the host launches rt blocks
   // more than there are tiles when the last wave of tiles would be at most half full; blocks F … nwg-1,
   // dispatched last, run the last rt tiles as 2·rt 128-row halves.
-  constexpr bool kHalfOK = !(EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL) && (ABL & 8) != 0 && (ABL & 16) == 0;
+  constexpr bool kHalfOK = !hq_epi_col_partials(EPI) && (ABL & 8) != 0 && (ABL & 16) == 0;
   const int ntiles = (M / BM) * tiles_n;
   const int rt = kHalfOK ? nwg - ntiles : 0;
   const int F = nwg - 2 * rt;                    // full-tile blocks (= ntiles - rt)
   const bool half = rt > 0 && bid >= F;
   const int nfull = rt > 0 ? F : nwg;
-  const int xcd = bid & 7, q = nfull >> 3, r = nfull & 7;
-  const int tile = half ? F + ((bid - F) >> 1) : (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int tile = half ? F + ((bid - F) >> 1) : hq_xcd_tile(bid, nfull);
   int tm = tile / tiles_n, tn = tile % tiles_n;
   if constexpr ((ABL & 16) != 0) {
     constexpr int GM = 8;
@@ -713,7 +635,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt2_kernel(const uint16_t* _
   constexpr int SEGS = WN / 8;                  // 8 pieces of 16 B per local row
   constexpr int ROWS_PER_IT = 64 / SEGS;        // 8
   constexpr int NIT = 128 / ROWS_PER_IT;        // 16 row-coalesced pieces per lane
-  constexpr bool kReadsAux = EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL || EPI == HQ_EPI_RESID || EPI == HQ_EPI_BDR;
+  constexpr bool kReadsAux = hq_epi_reads_aux(EPI);
   const int seg = lane % SEGS, rsub = lane / SEGS;
   const int gcol = n0 + wn * 64 + seg * 8;   // full 128-B lines per store (see gemm_nt3_kernel)
   auto grow_of = [&](int it) {
@@ -721,7 +643,8 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt2_kernel(const uint16_t* _
     return m0 + (lr >> 6) * 128 + wm * 64 + (lr & 63);
   };
   char* wreg = smem + wave * (128 * RS);
-  constexpr bool kBias = EPI == HQ_EPI_BIAS || EPI == HQ_EPI_GELU || EPI == HQ_EPI_GELUD || EPI == HQ_EPI_BDR;
+  // (bias-free epilogues: no "+0" canonicalise adds)
+  constexpr bool kBias = hq_epi_has_bias(EPI);
 #pragma unroll
   for (int J = 0; J < 4; ++J) {
     const int nh = J >> 1, j = J & 1;
@@ -742,7 +665,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt2_kernel(const uint16_t* _
   // a half tile has local rows 0..63 only (it < NIT / 2)
   uint4 aux[kReadsAux ? NIT : 1];
   if constexpr (kReadsAux) {
-    const uint16_t* src = (EPI == HQ_EPI_RESID || EPI == HQ_EPI_BDR) ? R : P;
+    const uint16_t* src = hq_epi_col_partials(EPI) ? P : R;
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {   // a half tile re-reads its rows for the unused pieces (no per-load branch)
       const int itl = half ? (it & (NIT / 2 - 1)) : it;
@@ -750,7 +673,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt2_kernel(const uint16_t* _
     }
   }
   float csum[8];
-  if constexpr (EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL) {
+  if constexpr (hq_epi_col_partials(EPI)) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) csum[e] = 0.f;
   }
@@ -760,50 +683,13 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt2_kernel(const uint16_t* _
     const int lr = it * ROWS_PER_IT + rsub;
     uint4 piece = *reinterpret_cast<const uint4*>(wreg + lr * RS + seg * 16);
     const size_t goff = (size_t)grow_of(it) * ldc + gcol;
-    if constexpr (EPI == HQ_EPI_GELU) {
-      *reinterpret_cast<uint4*>(P + goff) = piece;
-      float x[8];
-      hq_unpack8(piece, x);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) x[e] = gelu_erf(x[e]);
-      piece = hq_pack8(x);
-    } else if constexpr (EPI == HQ_EPI_GELUD) {
-      float x[8], g[8];
-      hq_unpack8(piece, x);
-      hq_gelu_grad8(x, g);   // g = gelu'(x), x = gelu(x)
-      *reinterpret_cast<uint4*>(P + goff) = hq_pack8(g);
-      piece = hq_pack8(x);
-    } else if constexpr (EPI == HQ_EPI_DMUL) {
-      float d[8], gd[8];
-      hq_unpack8(piece, d);
-      hq_unpack8(aux[it], gd);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { d[e] *= gd[e]; csum[e] += d[e]; }
-      piece = hq_pack8(d);
-    } else if constexpr (EPI == HQ_EPI_DGELU) {
-      float d[8], pr[8];
-      hq_unpack8(piece, d);
-      hq_unpack8(aux[it], pr);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) { d[e] *= gelu_grad(pr[e]); csum[e] += d[e]; }
-      piece = hq_pack8(d);
-    } else if constexpr (EPI == HQ_EPI_RESID) {
-      float d[8], rr[8];
-      hq_unpack8(piece, d);
-      hq_unpack8(aux[it], rr);
-#pragma unroll
-      for (int e = 0; e < 8; ++e) d[e] += rr[e];
-      piece = hq_pack8(d);
-    } else if constexpr (EPI == HQ_EPI_BDR) {
-      piece = hq_epi_bdr8(piece, aux[it], (uint32_t)goff, dr, key);
-    }
+    hq_epi_piece<EPI>(piece, [&]() -> const uint4& { return aux[it]; }, goff, dr, key, csum,
+                      [&](const uint4& p) { *reinterpret_cast<uint4*>(P + goff) = p; });
     *reinterpret_cast<uint4*>(C + goff) = piece;
   }
-  if constexpr (EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL) {
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      for (int o = SEGS; o < 64; o <<= 1) csum[e] += __shfl_xor(csum[e], o, 64);
-    __syncthreads();
+  if constexpr (hq_epi_col_partials(EPI)) {
+    hq_epi_csum_reduce<SEGS>(csum);
+    __syncthreads();   // red [2][BN] overlaps the staging regions
     float* red = reinterpret_cast<float*>(smem);  // [2][BN], indexed by tile column
     if (rsub == 0) {
 #pragma unroll
@@ -849,8 +735,8 @@ typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 #endif
 template <int EPI>
 struct NT3Epi {
-  static constexpr int kStores = (HQ_EPI_DIAG & 1) ? 0 : 16 * (1 + (EPI == HQ_EPI_GELU || EPI == HQ_EPI_GELUD ? 1 : 0));
-  static constexpr int kLoads = (EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL || EPI == HQ_EPI_RESID || EPI == HQ_EPI_BDR) ? 16 : 0;
+  static constexpr int kStores = (HQ_EPI_DIAG & 1) ? 0 : 16 * (1 + (hq_epi_writes_p(EPI) ? 1 : 0));
+  static constexpr int kLoads = hq_epi_reads_aux(EPI) ? 16 : 0;
   static constexpr int E = kStores + kLoads;   // vm ops per lane (the part store of waves 0-3 is not counted: a
 };                                             // smaller count only waits longer)
 
@@ -882,7 +768,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt3_kernel(const uint16_t* _
   constexpr int QREG = 32 * RS;
   constexpr int TAIL = BIASL + 1024;
   static_assert(3 * QREG <= PANEL / 2 && 2 * QREG <= REGION && TAIL + 3 * QREG <= 160 * 1024, "LDS plan");
-  constexpr bool kBiasE = EPI == HQ_EPI_BIAS || EPI == HQ_EPI_GELU || EPI == HQ_EPI_GELUD || EPI == HQ_EPI_BDR;
+  constexpr bool kBias = hq_epi_has_bias(EPI);
   const bool ht_on = (stagger >> 16) & 1;   // kHalfTail
   const bool quarter_on = (stagger >> 17) & 1;
   stagger &= 0xFF;
@@ -892,16 +778,15 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt3_kernel(const uint16_t* _
   const int wm = wave >> 2, wn = wave & 3;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int nwg = gridDim.x, bid = blockIdx.x, xcd = bid & 7;
+  const int id = hq_xcd_tile(bid, nwg);
   const int tiles_n = N / BN, ntiles = (M / BM) * tiles_n;
   // The epilogue's bias comes through LDS: wave 0 stages a unit's 256 values with one LDS-DMA instruction at the
   // unit's start (retired by the K-loop's counted waits, made visible by its barriers), and the epilogue reads
   // them with inline-asm ds_reads — a global load there would wait (vmcnt, in issue order) for the next tile's
   // K-tile-0 DMA still in flight, and a builtin LDS read makes hipcc drain vmcnt(0) for the same reason.
   auto stage_bias = [&](int n0u) {
-    if constexpr (kBiasE) {
+    if constexpr (kBias) {
       if (__builtin_amdgcn_readfirstlane(wave) == 0) {
         const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc((void*)bias, (short)0, N * 4, 0x00020000);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rb, (lds_void*)(smem + BIASL), 16, lane * 16, n0u * 4, 0, 0);
@@ -918,7 +803,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt3_kernel(const uint16_t* _
   // half tile keeps the full tile's load / barrier / wait sequence (its second 128 A rows are staged and
   // never read) and skips the m-half-1 MFMA phases, fragment reads and epilogue round.  Column partials
   // (DGELU / DMUL) are per 256-row block, so those epilogues never split.
-  constexpr bool kHalfOK = !(EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL);
+  constexpr bool kHalfOK = !hq_epi_col_partials(EPI);
   const int rtail = ntiles % nwg;
   const bool halftail = kHalfOK && ht_on && rtail > 0 && 2 * rtail <= nwg;
   const int F = halftail ? ntiles - rtail : ntiles;
@@ -1012,7 +897,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt3_kernel(const uint16_t* _
   HQ_DASSERT(tile < nunits);     // the host launches min(tiles, CUs) workgroups, so every one has a tile
   if (tile >= nunits) return;   // (unreachable; an early exit would skip the exit count that re-zeroes sched)
   int next = tile + nwg;
-  const int cnt_x = q + (xcd < r ? 1 : 0), base_x = id - (bid >> 3);
+  const int cnt_x = (nwg >> 3) + (xcd < (nwg & 7) ? 1 : 0), base_x = id - (bid >> 3);
   if constexpr (!DYN) sched = nullptr;
   unsigned* tix = sched ? sched + 32 * xcd : nullptr;
   // Phase offset for half of each XCD's workgroups (stagger × 8128 cycles): the tile seams of all CUs
@@ -1145,8 +1030,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt3_kernel(const uint16_t* _
     // DMA during the epilogue, and LDS executes a wave's ds operations in order, so a round's writes cannot
     // overtake the previous round's reads.
     constexpr int SEGS = WN / 8, ROWS_PER_IT = 64 / SEGS;
-    constexpr bool kReadsAux = EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL || EPI == HQ_EPI_RESID || EPI == HQ_EPI_BDR;
-    constexpr bool kBias = EPI == HQ_EPI_BIAS || EPI == HQ_EPI_GELU || EPI == HQ_EPI_GELUD || EPI == HQ_EPI_BDR;
+    constexpr bool kReadsAux = hq_epi_reads_aux(EPI);
     const int seg = lane % SEGS, rsub = lane / SEGS;
     // wave column wn owns the 64 contiguous tile columns wn·64 … +63 (B fragments nh·32 + j·16 inside it), so each
     // store instruction writes 8 rows × one full 128-B line — the earlier wn·32 + {0, 128} map wrote two 64-B half
@@ -1216,7 +1100,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt3_kernel(const uint16_t* _
       }
       const __amdgpu_buffer_rsrc_t rC = rsrc_of(C);
       const __amdgpu_buffer_rsrc_t rP = rsrc_of(P ? P : C);
-      const __amdgpu_buffer_rsrc_t rA = (EPI == HQ_EPI_RESID || EPI == HQ_EPI_BDR) ? rsrc_of(R) : rP;   // aux source
+      const __amdgpu_buffer_rsrc_t rA = hq_epi_col_partials(EPI) ? rP : rsrc_of(R);   // aux source
       constexpr int NQ = 2 * NR;   // 32-row rounds
       uint4 aux[kReadsAux ? (kAll ? 8 * NR : 4) : 1];
       // per round: stage (inline-asm ds_writes: no vmcnt fence), read its 4 pieces back, math, stores; the
@@ -1294,55 +1178,15 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt3_kernel(const uint16_t* _
 #pragma unroll
           for (int it = 0; it < 4; ++it) aux[it] = bload(rA, q, it);
         }
-        constexpr bool kTwo = EPI == HQ_EPI_GELU || EPI == HQ_EPI_GELUD;   // P and C stores per piece
+        constexpr bool kTwo = hq_epi_writes_p(EPI);   // P and C stores per piece
         u32x4_t holdP = {0u, 0u, 0u, 0u}, holdC = holdP;                    // the previous piece's store data
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
           uint4 piece = pieces[q][it];
           const size_t goff = goff_of(q, it);
-          const uint4 ax = aux[kAll ? q * 4 + it : (kReadsAux ? it : 0)];
           u32x4_t sP = holdP;
-          if constexpr (EPI == HQ_EPI_GELU) {
-            sP = bstore(rP, q, it, piece);
-            float x[8];
-            hq_unpack8(piece, x);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = gelu_erf(x[e]);
-            piece = hq_pack8(x);
-          } else if constexpr (EPI == HQ_EPI_GELUD) {
-            float x[8], g[8];
-            hq_unpack8(piece, x);
-#if HQ_EPI_DIAG & 2
-            for (int e = 0; e < 8; ++e) g[e] = x[e];
-#else
-            hq_gelu_grad8(x, g);   // g = gelu'(x), x = gelu(x)
-#endif
-            sP = bstore(rP, q, it, hq_pack8(g));
-            piece = hq_pack8(x);
-          } else if constexpr (EPI == HQ_EPI_DMUL) {
-            float d[8], gd[8];
-            hq_unpack8(piece, d);
-            hq_unpack8(ax, gd);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { d[e] *= gd[e]; csum[e] += d[e]; }
-            piece = hq_pack8(d);
-          } else if constexpr (EPI == HQ_EPI_DGELU) {
-            float d[8], pr[8];
-            hq_unpack8(piece, d);
-            hq_unpack8(ax, pr);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) { d[e] *= gelu_grad(pr[e]); csum[e] += d[e]; }
-            piece = hq_pack8(d);
-          } else if constexpr (EPI == HQ_EPI_RESID) {
-            float d[8], rr[8];
-            hq_unpack8(piece, d);
-            hq_unpack8(ax, rr);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) d[e] += rr[e];
-            piece = hq_pack8(d);
-          } else if constexpr (EPI == HQ_EPI_BDR) {
-            piece = hq_epi_bdr8(piece, ax, (uint32_t)goff, dr, key);
-          }
+          hq_epi_piece<EPI, (HQ_EPI_DIAG & 2) != 0>(piece, [&] { return aux[kAll ? q * 4 + it : it]; }, goff, dr, key, csum,
+                                                    [&](const uint4& p) { sP = bstore(rP, q, it, p); });
           const u32x4_t sC = bstore(rC, q, it, piece);
           if (it > 0) {
             if constexpr (kTwo) asm volatile("" :: "v"(holdP), "v"(holdC));
@@ -1352,7 +1196,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt3_kernel(const uint16_t* _
           holdC = sC;
           // column-partial epilogues: one piece at a time (hipcc otherwise computes every piece's products
           // ahead of the serial csum chain and spills them)
-          if constexpr (EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL) __builtin_amdgcn_sched_barrier(0);
+          if constexpr (hq_epi_col_partials(EPI)) __builtin_amdgcn_sched_barrier(0);
         }
         // round end: 64 wait states with the last stores' data held (BIAS stores back to back: all 4 pieces)
 #define HQ_PAD64 "s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15"
@@ -1370,10 +1214,8 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_nt3_kernel(const uint16_t* _
     if constexpr (!kHalfOK) epilogue(std::integral_constant<int, 2>{});   // column partials: never a half tile
     else if (half) epilogue(std::integral_constant<int, 1>{});
     else epilogue(std::integral_constant<int, 2>{});
-    if constexpr (EPI == HQ_EPI_DGELU || EPI == HQ_EPI_DMUL) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-        for (int o = SEGS; o < 64; o <<= 1) csum[e] += __shfl_xor(csum[e], o, 64);
+    if constexpr (hq_epi_col_partials(EPI)) {
+      hq_epi_csum_reduce<SEGS>(csum);
       float* red = reinterpret_cast<float*>(smem + SPARE + REGION);  // [2][BN], by tile column
       if (rsub == 0) {
 #pragma unroll
@@ -1469,18 +1311,24 @@ unsigned* nt3_sched_slot(hipStream_t s) {
   return p->base + kSchedWords * (p->streams.size() - 1);
 }
 
-// vS split-K factor: only epilogues without column partials / GELU, grids below half a workgroup per CU,
+// vS split-K factor (epilogues that can split: nts_can_split): grids below half a workgroup per CU,
 // and at least 8 K-tiles per split; HQ_GEMM_SPLITK=0 disables (A/B), N > 1 forces up to N.
 int g_nts_splitk = [] {
   const char* e = getenv("HQ_GEMM_SPLITK");
   return e ? atoi(e) : -1;
 }();
-template <int EPI>
-int nts_ksplit(int tiles, int nk) {
-  if (!(EPI == HQ_EPI_NONE || EPI == HQ_EPI_BIAS || EPI == HQ_EPI_RESID) || g_nts_splitk == 0) return 1;
+int nts_ksplit(int epi, int tiles, int nk) {
+  if (!nts_can_split(epi) || g_nts_splitk == 0) return 1;
   int ks = g_nts_splitk > 1 ? g_nts_splitk : (2 * tiles <= hq_num_cus() ? 2 * hq_num_cus() / tiles : 1);
   ks = std::min(ks, std::min(4, nk / 8));
   return ks > 1 ? ks : 1;
+}
+
+// Half-tile tail of v3 and v2: the last wave of `grid` 256² tiles is at most half full (and not the only wave), so
+// its tiles run as 128-row halves.  Column partials are per 256-row block: those epilogues never split.
+bool half_tile_tail(int epi, int grid) {
+  const int ncu = hq_num_cus(), rt = grid % ncu;
+  return (g_gemm_stagger & kHalfTail) && !hq_epi_col_partials(epi) && rt > 0 && 2 * rt <= ncu && grid > ncu;
 }
 
 constexpr size_t epi_lds(int bn) {
@@ -1495,13 +1343,9 @@ void launch_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const float* 
                 float* ws) {
   if (bn == 1) {   // vS: 128×128 tiles, M tail
     constexpr size_t lds = 2 * 2 * 128 * 128;
-    static bool init = [] {
-      (void)hipFuncSetAttribute((const void*)gemm_nts_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      return true;
-    }();
-    (void)init;
+    [[maybe_unused]] static const bool once = hq_raise_lds_limit({(const void*)gemm_nts_kernel<EPI>}, lds);
     const int grid_s = ((M + 127) / 128) * (N / 128);
-    int ks = nts_ksplit<EPI>(grid_s, K / BK);
+    int ks = nts_ksplit(EPI, grid_s, K / BK);
     if (ks > 1 && !ws) {   // no workspace from the caller: run unsplit rather than share a scratch buffer
       ks = 1;
     }
@@ -1510,9 +1354,8 @@ void launch_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const float* 
     if (ks > 1) {
       const size_t n8 = (size_t)M * N / 8;
       const int g = (int)std::min<size_t>((n8 + 255) / 256, 2048);
-      hipLaunchKernelGGL((splitk_epi_kernel<EPI == HQ_EPI_BIAS ? HQ_EPI_BIAS : EPI == HQ_EPI_RESID ? HQ_EPI_RESID
-                                                                                                   : HQ_EPI_NONE>),
-                         dim3(g), dim3(256), 0, s, ws, ks, C, bias, R, M, N, ldc);
+      hipLaunchKernelGGL((splitk_epi_kernel<nts_can_split(EPI) ? EPI : HQ_EPI_NONE>), dim3(g), dim3(256), 0, s, ws, ks, C,
+                         bias, R, M, N, ldc);
     }
     return;
   }
@@ -1522,25 +1365,18 @@ void launch_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const float* 
   // K = 768 / 2304 on the b256 shapes, -1-3 % at K = 3072: tools/gemm_nt3_check.py, profiles/s3_gemm_v3)
   // (and at any K when the half-tile tail applies: at K = 3072 v3 + tail beat v2 + tail by 0.2-2.8 % on two
   // boxes, profiles/r3_halftail)
-  const int ncu_t = hq_num_cus(), rt_t = grid % ncu_t;
-  const bool tail_t = (g_gemm_stagger & kHalfTail) && EPI != HQ_EPI_DGELU && EPI != HQ_EPI_DMUL && rt_t > 0 &&
-                      2 * rt_t <= ncu_t && grid > ncu_t;
-  const bool v3_auto = g_gemm_variant == 0 && (K <= 2304 || tail_t);
+  const bool tail = half_tile_tail(EPI, grid);
+  const bool v3_auto = g_gemm_variant == 0 && (K <= 2304 || tail);
   if (bn == 256 && (g_gemm_variant == 3 || v3_auto) && K >= 2 * BK && srd_ok) {
     constexpr size_t lds = 2 * 2 * 256 * 128 + 64 * 144 + 2 * 256 * 4 + 16 + 1024 + 3 * 32 * 144;
-    static bool init = [] {
-      for (const void* f : {(const void*)gemm_nt3_kernel<EPI, false, false>, (const void*)gemm_nt3_kernel<EPI, true, false>,
-                            (const void*)gemm_nt3_kernel<EPI, false, true>, (const void*)gemm_nt3_kernel<EPI, true, true>})
-        (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      return true;
-    }();
-    (void)init;
-    const int nwg = std::min(grid, ncu_t);
+    [[maybe_unused]] static const bool once = hq_raise_lds_limit(
+        {(const void*)gemm_nt3_kernel<EPI, false, false>, (const void*)gemm_nt3_kernel<EPI, true, false>,
+         (const void*)gemm_nt3_kernel<EPI, false, true>, (const void*)gemm_nt3_kernel<EPI, true, true>}, lds);
+    const int nwg = std::min(grid, hq_num_cus());
     unsigned* sched = (g_gemm_sched && grid > 2 * nwg) ? nt3_sched_slot(s) : nullptr;
     // streamed (nt | sc1) epilogue stores: epilogues without an operand load, K <= 768 (g_store_policy 1), or at any K
     // (2, A/B only), or never (0)
-    constexpr bool kNoAux = EPI == HQ_EPI_NONE || EPI == HQ_EPI_BIAS || EPI == HQ_EPI_GELU || EPI == HQ_EPI_GELUD;
-    const bool nts = kNoAux && (g_store_policy == 2 || (g_store_policy == 1 && K <= 768));
+    const bool nts = !hq_epi_reads_aux(EPI) && (g_store_policy == 2 || (g_store_policy == 1 && K <= 768));
     auto go = [&](auto kern, unsigned* sc) {
       hipLaunchKernelGGL(kern, dim3(nwg), dim3(kThreads), lds, s, A, B, C, bias, P, R, part, M, N, K, lda, ldb, ldc,
                          g_gemm_stagger, sc, dr);
@@ -1555,42 +1391,32 @@ void launch_epi(const uint16_t* A, const uint16_t* B, uint16_t* C, const float* 
     // tools/gemm_lab); grouped 8-row-panel tile order only for wide N (+15 % at 8192², neutral at
     // N <= 3072 where an XCD's co-resident tiles already share few panels).
     constexpr size_t lds = epi_lds(256);
-    static bool init = [] {
-      (void)hipFuncSetAttribute((const void*)gemm_nt2_kernel<EPI, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      (void)hipFuncSetAttribute((const void*)gemm_nt2_kernel<EPI, 24>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      return true;
-    }();
-    (void)init;
+    [[maybe_unused]] static const bool once =
+        hq_raise_lds_limit({(const void*)gemm_nt2_kernel<EPI, 8>, (const void*)gemm_nt2_kernel<EPI, 24>}, lds);
     if (N / 256 >= 16) {
       hipLaunchKernelGGL((gemm_nt2_kernel<EPI, 24>), dim3(grid), dim3(kThreads), lds, s, A, B, C, bias, P, R, part, M, N, K,
                          lda, ldb, ldc, dr);
     } else {
-      // half-tile tail: rt more blocks, the last 2·rt of them halves of the last rt tiles
-      const int ncu = hq_num_cus(), rt = grid % ncu;
-      const bool ht = (g_gemm_stagger & kHalfTail) && EPI != HQ_EPI_DGELU && EPI != HQ_EPI_DMUL && rt > 0 &&
-                      2 * rt <= ncu && grid > ncu;
-      hipLaunchKernelGGL((gemm_nt2_kernel<EPI, 8>), dim3(ht ? grid + rt : grid), dim3(kThreads), lds, s, A, B, C, bias, P,
-                         R, part, M, N, K, lda, ldb, ldc, dr);
+      // half-tile tail: rt = grid % CUs more blocks, the last 2·rt of them halves of the last rt tiles
+      hipLaunchKernelGGL((gemm_nt2_kernel<EPI, 8>), dim3(tail ? grid + grid % hq_num_cus() : grid), dim3(kThreads), lds, s,
+                         A, B, C, bias, P, R, part, M, N, K, lda, ldb, ldc, dr);
     }
-  } else if (bn == 256) {
-    constexpr size_t lds = epi_lds(256);
-    static bool init = [] {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<EPI, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      return true;
-    }();
-    (void)init;
-    hipLaunchKernelGGL((gemm_nt_kernel<EPI, 256>), dim3(grid), dim3(kThreads), lds, s, A, B, C, bias, P, R, part, M, N, K,
-                       lda, ldb, ldc, dr);
-  } else {
-    constexpr size_t lds = epi_lds(128);
-    static bool init = [] {
-      (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<EPI, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      return true;
-    }();
-    (void)init;
-    hipLaunchKernelGGL((gemm_nt_kernel<EPI, 128>), dim3(grid), dim3(kThreads), lds, s, A, B, C, bias, P, R, part, M, N, K,
-                       lda, ldb, ldc, dr);
+  } else {   // v1: N % 256 != 0 (128-wide blocks), K = 64, or forced
+    auto v1 = [&](auto bn_c) {
+      constexpr int BN = decltype(bn_c)::value;
+      constexpr size_t lds = epi_lds(BN);
+      [[maybe_unused]] static const bool once = hq_raise_lds_limit({(const void*)gemm_nt_kernel<EPI, BN>}, lds);
+      hipLaunchKernelGGL((gemm_nt_kernel<EPI, BN>), dim3(grid), dim3(kThreads), lds, s, A, B, C, bias, P, R, part, M, N, K,
+                         lda, ldb, ldc, dr);
+    };
+    if (bn == 256) v1(std::integral_constant<int, 256>{}); else v1(std::integral_constant<int, 128>{});
   }
+}
+
+// f(std::integral_constant<int, EPI>) for the runtime epilogue code `epi`
+template <class F, int... E>
+void with_epi(int epi, F&& f, std::integer_sequence<int, E...>) {
+  ((epi == E ? f(std::integral_constant<int, E>{}) : (void)0), ...);
 }
 
 }  // namespace
@@ -1629,13 +1455,7 @@ int hq_gemm_nt_part_rows(int M, int N, int K) {
 size_t hq_gemm_nt_ws_floats(int M, int N, int K, int epi) {
   if (hq_gemm_nt_supported(M, N, K) != 1) return 0;   // split-K exists on the 128² (vS) kernel only
   const int grid_s = ((M + 127) / 128) * (N / 128);
-  int ks = 1;
-  switch (epi) {
-    case HQ_EPI_NONE: ks = nts_ksplit<HQ_EPI_NONE>(grid_s, K / BK); break;
-    case HQ_EPI_BIAS: ks = nts_ksplit<HQ_EPI_BIAS>(grid_s, K / BK); break;
-    case HQ_EPI_RESID: ks = nts_ksplit<HQ_EPI_RESID>(grid_s, K / BK); break;
-    default: ks = 1;
-  }
+  const int ks = nts_ksplit(epi, grid_s, K / BK);
   return ks > 1 ? (size_t)ks * M * N : 0;
 }
 
@@ -1647,14 +1467,7 @@ void hq_gemm_nt(const uint16_t* A, const uint16_t* B, uint16_t* C, const float* 
     dr.thr = hq_threshold(drop_p);
     dr.ks = hq_keep_scale(dr.thr);
   }
-  switch (epi) {
-    case HQ_EPI_NONE: launch_epi<HQ_EPI_NONE>(A, B, C, bias, P, R, part, M, N, K, lda, ldb, ldc, bn, s, dr, ws); break;
-    case HQ_EPI_BIAS: launch_epi<HQ_EPI_BIAS>(A, B, C, bias, P, R, part, M, N, K, lda, ldb, ldc, bn, s, dr, ws); break;
-    case HQ_EPI_GELU: launch_epi<HQ_EPI_GELU>(A, B, C, bias, P, R, part, M, N, K, lda, ldb, ldc, bn, s, dr, ws); break;
-    case HQ_EPI_DGELU: launch_epi<HQ_EPI_DGELU>(A, B, C, bias, P, R, part, M, N, K, lda, ldb, ldc, bn, s, dr, ws); break;
-    case HQ_EPI_RESID: launch_epi<HQ_EPI_RESID>(A, B, C, bias, P, R, part, M, N, K, lda, ldb, ldc, bn, s, dr, ws); break;
-    case HQ_EPI_GELUD: launch_epi<HQ_EPI_GELUD>(A, B, C, bias, P, R, part, M, N, K, lda, ldb, ldc, bn, s, dr, ws); break;
-    case HQ_EPI_DMUL: launch_epi<HQ_EPI_DMUL>(A, B, C, bias, P, R, part, M, N, K, lda, ldb, ldc, bn, s, dr, ws); break;
-    case HQ_EPI_BDR: launch_epi<HQ_EPI_BDR>(A, B, C, bias, P, R, part, M, N, K, lda, ldb, ldc, bn, s, dr, ws); break;
-  }
+  with_epi(epi, [&](auto e) {
+    launch_epi<decltype(e)::value>(A, B, C, bias, P, R, part, M, N, K, lda, ldb, ldc, bn, s, dr, ws);
+  }, std::make_integer_sequence<int, HQ_EPI_BDR + 1>{});
 }

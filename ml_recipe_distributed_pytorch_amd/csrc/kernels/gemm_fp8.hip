@@ -26,6 +26,7 @@
 #include <algorithm>
 
 #include "hq_common.h"
+#include "hq_gemm_epi.h"
 #include "hq_kernels.h"
 
 namespace {
@@ -94,14 +95,7 @@ template <int EPI, bool Q8, bool WC, bool GD8>
 __device__ __forceinline__ void epi_piece(uint4 piece, const uint4& aux, size_t goff, uint16_t* __restrict__ C,
                                           uint16_t* __restrict__ P, uint8_t* __restrict__ C8, float inv8, float& amax,
                                           float (&csum)[8]) {
-  if constexpr (EPI == HQ_EPI_RESID) {
-    float d[8], rr[8];
-    hq_unpack8(piece, d);
-    hq_unpack8(aux, rr);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) d[e] += rr[e];
-    piece = hq_pack8(d);
-  } else if constexpr (EPI == HQ_EPI_DMUL) {
+  if constexpr (EPI == HQ_EPI_DMUL) {
     // no fma contraction of d·gd into the column sum: hipcc contracted it in one kernel form and not the
     // other, and the per-tile / persistent partials must agree bit for bit
 #pragma clang fp contract(off)
@@ -133,6 +127,8 @@ __device__ __forceinline__ void epi_piece(uint4 piece, const uint4& aux, size_t 
       for (int e = 0; e < 8; ++e) amax = fmaxf(amax, fabsf(f[e]));
       *reinterpret_cast<uint2*>(C8 + goff) = make_uint2(hq_pack_fp8x4(f, inv8), hq_pack_fp8x4(f + 4, inv8));
     }
+  } else {   // RESID (NONE / BIAS: nothing to do) as in the bf16 kernels
+    hq_epi_piece<EPI>(piece, [&]() -> const uint4& { return aux; }, goff, HqDropArg{}, 0u, csum, [](const uint4&) {});
   }
   if constexpr (WC) *reinterpret_cast<uint4*>(C + goff) = piece;
 }
@@ -152,9 +148,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_kernel(const uint8_t* __
   const int wm = wave >> 2, wn = wave & 3;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int tile = hq_xcd_tile(blockIdx.x, gridDim.x);
   const int tiles_n = N / BN;
   const int tm = tile / tiles_n, tn = tile % tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
@@ -310,9 +304,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_kernel(const uint8_t* __
     if (lane == 0) part8[blockIdx.x * (kThreads / 64) + wave] = amax;
   }
   if constexpr (EPI == HQ_EPI_DMUL) {   // column sums of dpre over this tile's 256 rows -> part[tm][n]
-#pragma unroll
-    for (int e = 0; e < 8; ++e)
-      for (int o = SEGS; o < 64; o <<= 1) csum[e] += __shfl_xor(csum[e], o, 64);
+    hq_epi_csum_reduce<SEGS>(csum);
     __syncthreads();
     float* red = reinterpret_cast<float*>(smem);  // [2][BN] by tile column, one row per wm
     if (rsub == 0) {
@@ -360,9 +352,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8p_kernel(const uint8_t* _
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 2, wn = wave & 3;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-  const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+  const int nwg = gridDim.x, id = hq_xcd_tile(blockIdx.x, nwg);
   const int tiles_n = N / BN, ntiles = (M / BM) * tiles_n;
   const int nt = K / BK;
   const int lda = K, ldb = K, ldc = N;
@@ -544,6 +534,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8p_kernel(const uint8_t* _
       }
     }
     if constexpr (EPI == HQ_EPI_DMUL) {
+      // (hq_epi_csum_reduce, spelled out: through the call hipcc schedules this kernel differently)
 #pragma unroll
       for (int e = 0; e < 8; ++e)
         for (int o = SEGS; o < 64; o <<= 1) csum[e] += __shfl_xor(csum[e], o, 64);
@@ -591,11 +582,7 @@ void launch(const uint8_t* A, const uint8_t* B, uint16_t* C, const float* bias, 
   const bool persist = g_fp8_variant == 3 || (g_fp8_variant == 0 && !(EPI == HQ_EPI_DMUL && Q8));
   if (persist) {
     constexpr size_t lds = 2 * (size_t)(2 * 256 * 128) + 64 * (64 * 2 + 16) + 2 * BN * 4;
-    static bool init = [] {
-      (void)hipFuncSetAttribute((const void*)gemm_fp8p_kernel<EPI, Q8, WC, GD8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      return true;
-    }();
-    (void)init;
+    [[maybe_unused]] static const bool once = hq_raise_lds_limit({(const void*)gemm_fp8p_kernel<EPI, Q8, WC, GD8>}, lds);
     const int tiles = (M / BM) * (N / BN);
     const int nwg = std::min(tiles, hq_num_cus());   // every workgroup has at least one tile
     float* part8 = Q8 ? hq_fp8_amax_parts((size_t)nwg * (kThreads / 64), q8, s) : nullptr;
@@ -605,11 +592,7 @@ void launch(const uint8_t* A, const uint8_t* B, uint16_t* C, const float* bias, 
     return;
   }
   constexpr size_t lds = lds_bytes();
-  static bool init = [] {
-    (void)hipFuncSetAttribute((const void*)gemm_fp8_kernel<EPI, Q8, WC, GD8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return true;
-  }();
-  (void)init;
+  [[maybe_unused]] static const bool once = hq_raise_lds_limit({(const void*)gemm_fp8_kernel<EPI, Q8, WC, GD8>}, lds);
   const int grid = (M / BM) * (N / BN);
   float* part8 = Q8 ? hq_fp8_amax_parts((size_t)grid * (kThreads / 64), q8, s) : nullptr;
   hipLaunchKernelGGL((gemm_fp8_kernel<EPI, Q8, WC, GD8>), dim3(grid), dim3(kThreads), lds, s, A, B, C, bias, P, sa, sb,

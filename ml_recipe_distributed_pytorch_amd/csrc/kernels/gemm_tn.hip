@@ -82,8 +82,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const uint16_t* __
   // bijective XCD remap; consecutive ids on an XCD = the same token range (split) over neighbouring
   // output tiles, so co-resident blocks share their dy / x slabs through that XCD's L2
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int id = hq_xcd_tile(bid, nwg);
   const int tiles = nwg / S;
   const int split = id / tiles, tile = id % tiles;
   const int n0 = (tile / tiles_k) * 256, k0 = (tile % tiles_k) * 256;
@@ -278,8 +277,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn2_kernel(const uint16_t* _
   const int wm = wave >> 2, wn = wave & 3;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int id = hq_xcd_tile(bid, nwg);
   const int tiles = nwg / S;
   const int split = id / tiles, tile = id % tiles;
   const int n0 = (tile / tiles_k) * 256, k0 = (tile % tiles_k) * 256;
@@ -476,8 +474,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn8_kernel(const uint8_t* __
   const int wm = wave >> 2, wn = wave & 3;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const int nwg = gridDim.x, bid = blockIdx.x;
-  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-  const int id = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int id = hq_xcd_tile(bid, nwg);
   const int tiles = nwg / S;
   const int split = id / tiles, tile = id % tiles;
   const int n0 = (tile / tiles_k) * 256, k0 = (tile % tiles_k) * 256;
@@ -646,16 +643,9 @@ void hq_gemm_tn_set_variant(int v) { g_tn_variant = v; }
 void hq_gemm_tn(const uint16_t* A, const uint16_t* B, float* part, float* out, float* bpart, float* bout, int T, int N, int K,
                 int S, bool accumulate, hipStream_t s) {
   constexpr size_t lds = 2 * STAGE;
-  static bool init = [] {
-    (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<0, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)gemm_tn2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)gemm_tn2_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)gemm_tn2_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    (void)hipFuncSetAttribute((const void*)gemm_tn2_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return true;
-  }();
-  (void)init;
+  [[maybe_unused]] static const bool once = hq_raise_lds_limit(
+      {(const void*)gemm_tn_kernel<0, false>, (const void*)gemm_tn_kernel<0, true>, (const void*)gemm_tn2_kernel<0>,
+       (const void*)gemm_tn2_kernel<1>, (const void*)gemm_tn2_kernel<2>, (const void*)gemm_tn2_kernel<3>}, lds);
   const int tiles_k = (K + 255) / 256, tiles = ((N + 255) / 256) * tiles_k;
   if (bout)
     hipLaunchKernelGGL((gemm_tn_kernel<0, true>), dim3(tiles * S), dim3(kThreads), lds, s, A, B, part, bpart, T, N, K, S,
@@ -692,11 +682,7 @@ int hq_gemm_tn8_splits(int T, int N, int K) {
 void hq_gemm_tn8(const uint8_t* A, const uint8_t* B, const float* sa, const float* sb, float* part, float* out, int T,
                  int N, int K, int S, bool accumulate, hipStream_t s) {
   constexpr size_t lds = 2 * STAGE;
-  static bool init = [] {
-    (void)hipFuncSetAttribute((const void*)gemm_tn8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    return true;
-  }();
-  (void)init;
+  [[maybe_unused]] static const bool once = hq_raise_lds_limit({(const void*)gemm_tn8_kernel}, lds);
   const int tiles_k = (K + 255) / 256, tiles = ((N + 255) / 256) * tiles_k;
   hipLaunchKernelGGL(gemm_tn8_kernel, dim3(tiles * S), dim3(kThreads), lds, s, A, B, part, sa, sb, T, N, K, S, tiles_k);
   const size_t n4 = (size_t)N * K / 4;

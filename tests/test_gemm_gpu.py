@@ -384,3 +384,57 @@ def test_gemm_nt_persistent_every_epilogue_full_output(cuda, M, N, K, variant):
     pf = pre.float()
     gelu_grad = 0.5 * (1 + torch.erf(pf / 2 ** 0.5)) + pf * torch.exp(-0.5 * pf * pf) / (2 * torch.pi) ** 0.5
     _close(d2, ref.bfloat16().float() * gelu_grad)
+
+
+# (epilogue, variant) pairs whose C or P already differed from v1's before the epilogue was shared; none
+_VARIANTS_DIFFER = {}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,N,K", [(256, 256, 128), (512, 512, 192)])
+def test_gemm_nt_variants_agree_bitwise(cuda, M, N, K, variant):
+    """v1, v2, v3 and vS share one epilogue and accumulate K in the same order: at the smallest shapes all four
+    serve (v3 needs K >= 128, the 256-row kernels M, N % 256 == 0) C of every epilogue, and P of GELU / GELUD, is
+    bitwise equal across them.  The column partials are not (vS sums 128-row blocks, and the contraction of the
+    sum is per kernel): they are held to the column sums of C."""
+    if variant:
+        pytest.skip("the kernel variants are selected below")
+    EPI_GELUD, EPI_DMUL, EPI_BDR = 5, 6, 7
+    k = _native.kernels()
+    g = torch.Generator(device=cuda).manual_seed(M + N + K)
+    A = (torch.randn(M, K, device=cuda, generator=g) * 0.5).bfloat16()
+    B = (torch.randn(N, K, device=cuda, generator=g) * 0.1).bfloat16()
+    bias = torch.randn(N, device=cuda, generator=g) * 0.1
+    resid = torch.randn(M, N, device=cuda, generator=g).bfloat16()
+    pre = (torch.randn(M, N, device=cuda, generator=g) * 0.5).bfloat16()   # DGELU's stored pre-activation
+    gd = torch.rand(M, N, device=cuda, generator=g).bfloat16()             # DMUL's stored gelu'
+    cases = {EPI_NONE: {}, EPI_BIAS: dict(bias=bias), EPI_GELU: dict(bias=bias), EPI_GELUD: dict(bias=bias),
+             EPI_DGELU: dict(pre=pre), EPI_DMUL: dict(pre=gd), EPI_RESID: dict(resid=resid),
+             EPI_BDR: dict(bias=bias, resid=resid, p=0.1, seed=3, opid=5)}
+    differ = []   # (epilogue, variant, output, largest difference from v1)
+    try:
+        for epi, kw in cases.items():
+            outs = {}
+            for v in (1, 2, 3, 4):
+                k.gemm_set_variant(v)
+                kk = dict(kw)
+                if epi in (EPI_GELU, EPI_GELUD):
+                    kk["pre"] = torch.empty(M, N, device=cuda, dtype=torch.bfloat16)
+                if epi in (EPI_DGELU, EPI_DMUL):
+                    kk["part"] = torch.empty(k.gemm_nt_part_rows(M, N, K), N, device=cuda)
+                c = k.gemm_nt(A, B, epi, **kk)
+                torch.cuda.synchronize()
+                outs[v] = (c, kk["pre"] if epi in (EPI_GELU, EPI_GELUD) else None)
+                if "part" in kk:
+                    cs = c.float().sum(0)
+                    torch.testing.assert_close(kk["part"].sum(0), cs, rtol=2e-2,
+                                               atol=5e-2 * (1 + c.float().abs().sum(0).max().item() / M))
+            for v in (2, 3, 4):
+                if (epi, v) in _VARIANTS_DIFFER:
+                    continue
+                for name, a, b in zip("CP", outs[1], outs[v]):
+                    if a is not None and not torch.equal(a, b):
+                        differ.append((epi, v, name, (a.float() - b.float()).abs().max().item()))
+    finally:
+        k.gemm_set_variant(0)
+    assert not differ, f"(epilogue, variant, output, max difference from v1): {differ}"
