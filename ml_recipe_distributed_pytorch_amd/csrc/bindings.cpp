@@ -1002,7 +1002,7 @@ Tensor qa_heads_bwd(Tensor seq, int64_t L, Tensor dlog, Tensor dheads, c10::opti
 
 }  // namespace
 
-// ---------------------------------------------------------------- --precision fp32 (f32_ops.hip)
+// ---------------------------------------------------------------- --precision fp32 (f32_*.hip)
 static void f32_rows(const Tensor& t, const char* n) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == F32 && t.is_contiguous(), n, " must be a contiguous fp32 GPU tensor");
 }
@@ -1048,7 +1048,7 @@ void f32_embed_bwd(Tensor dy, Tensor ids, Tensor pids, Tensor tids, Tensor ww, T
     const int V = (int)ww.size(0), P = (int)wp.size(0);
     size_t sort_bytes = std::max(hq_sort_ids_bytes((int)T, V), hq_sort_ids_bytes((int)T, P));
     if (n_types > 2) sort_bytes = std::max(sort_bytes, hq_sort_ids_bytes((int)T, n_types));
-    es = emb_scratch(ids, dy.options(), T, H, sort_bytes, std::max(hq_f32_embed_run_chunks((int)T), 1), nullptr);
+    es = emb_scratch(ids, dy.options(), T, H, sort_bytes, std::max(hq_emb_run_chunks((int)T), 1), nullptr);
   }
   float* t0 = ptr<float>(g_type);
   hq_f32_embed_bwd(ptr<float>(dy), ptr<int64_t>(ids), ptr<int64_t>(pids), ptr<int64_t>(tids), ptr<float>(ww), ptr<float>(wp),

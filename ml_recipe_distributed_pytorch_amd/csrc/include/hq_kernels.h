@@ -86,9 +86,11 @@ struct HqEmbScratchSizes {
   int chunks, pos_rows;
 };
 HqEmbScratchSizes hq_embed_bwd_scratch(int T, int V, int L, int P);
-// sorted rows per wave of the sorted-run kernels (embed_word_kernel here, f32_ops.hip f32_embed_run_kernel): the
+// sorted rows per wave of the sorted-run kernels (embed_word_kernel here, f32_embed.hip f32_embed_run_kernel): the
 // unit of their documented summation order
 constexpr int kHqEmbRunChunk = 16;
+// chunks of the sorted list of T tokens: waves of a sorted-run launch, and rows / 2 of the carry buffer [chunks][2][H]
+inline int hq_emb_run_chunks(int T) { return (T + kHqEmbRunChunk - 1) / kHqEmbRunChunk; }
 // det_pos: every position gradient from a sort of pids + the sorted-run kernels (no position partials, no position
 // atomics); det_type: with n_types > 2 the type gradients likewise from a sort of tids.  Either needs sort_tmp to
 // cover hq_sort_ids_bytes(T, P) / (T, n_types) as well.
@@ -100,30 +102,34 @@ void hq_embed_bwd(const uint16_t* dy, const int64_t* ids, const int64_t* pids, c
 // partial-sum rows embed_bwd needs for T tokens laid out as [T / L][L] (L <= 0: one sequence)
 int hq_embed_bwd_partials(int T, int L);
 
-// ---- f32_ops.hip: --precision fp32 row-wise ops and flash attention ----------------------------------------------
+// ---- --precision fp32 row-wise ops and flash attention: f32_embed.hip, f32_norm.hip, f32_rowops.hip, f32_attention.hip
+// f32_rowops.hip
 int hq_f32_row_partials(int T);   // partial rows of the column-partial kernels for T rows
 int hq_f32_part_rows(int T);      // rows to allocate for their `part` scratch (partials + the fold's level 1)
+// f32_embed.hip
 void hq_f32_embed_fwd(const int64_t* ids, const int64_t* pids, const int64_t* tids, const float* ww, const float* wp,
                       const float* wt, const float* gamma, const float* beta, float* y, float* mean, float* rstd, int T, int H,
                       float eps, float p, uint32_t seed, uint32_t opid, int V, int P, int NTY, hipStream_t s);
 // det != null: no float atomics — every table row is summed over its key-sorted run in a fixed order.  Scratch:
 // keys / rows / skeys / srows [T], sort_tmp of the largest hq_sort_ids_bytes(T, V | P | NTY), carry
-// [hq_f32_embed_run_chunks(T)][2][H]; ppart unused.
+// [hq_emb_run_chunks(T)][2][H]; ppart unused.
 void hq_f32_embed_bwd(const float* dy, const int64_t* ids, const int64_t* pids, const int64_t* tids, const float* ww,
                       const float* wp, const float* wt, const float* gamma, const float* mean, const float* rstd,
                       float* g_word, float* g_pos, float* g_type, float* part, HqOuts outs, int T, int H, int pad_word,
                       int pad_pos, float p, uint32_t seed, uint32_t opid, bool accumulate, int V, int P, int NTY,
                       hipStream_t s, const HqEmbScratch* det = nullptr);
-int hq_f32_embed_run_chunks(int T);
+// f32_norm.hip
 void hq_f32_ln_fwd(const float* a, const float* resid, const float* gamma, const float* beta, float* y, float* z, float* mean,
                    float* rstd, int T, int H, float eps, float p, uint32_t seed, uint32_t opid, hipStream_t s);
 void hq_f32_ln_bwd(const float* dy, const float* dy2, const float* z, const float* gamma, const float* beta, const float* mean,
                    const float* rstd, float* dz, float* da, float* part, HqOuts outs, int T, int H, float p, uint32_t seed,
                    uint32_t opid, bool accumulate, hipStream_t s);
+// f32_rowops.hip
 void hq_f32_gelu_fwd(const float* x, float* y, size_t n, hipStream_t s);
 void hq_f32_gelu_bwd(const float* dout, const float* x, float* d, float* part, float* g_bias, int T, int N, bool accumulate,
                      hipStream_t s);
 void hq_f32_colsum(const float* x, float* part, float* out, int T, int N, bool accumulate, hipStream_t s);
+// f32_attention.hip
 void hq_f32_attn_fwd(const float* qkv, const float* key_bias, float* ctx, float* lse, int B, int L, int nh, float p,
                      uint32_t seed, uint32_t opid, float scale, hipStream_t s);
 void hq_f32_attn_bwd(const float* dctx, const float* qkv, const float* ctx, const float* lse, const float* key_bias,

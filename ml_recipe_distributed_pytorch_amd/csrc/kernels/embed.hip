@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(
 }
 
 // ---- table gradients over key-sorted runs (this file's embed_word_kernel / embed_carry_kernel and the fp32 pair
-// f32_embed_run_kernel / f32_embed_carry_kernel of f32_ops.hip) -------------------------------------------------
+// f32_embed_run_kernel / f32_embed_carry_kernel of f32_embed.hip) -----------------------------------------------
 // One pair of kernels serves the word, position and type tables; KEY picks which id of a token is the key
 // (0: ids, 1: pids, 2: tids).  The tokens are sorted by key with the stable hq_sort_ids, so the tokens of one key
 // (its "run") are contiguous in the sorted list and stay in token order.  The summation order of a table row is:

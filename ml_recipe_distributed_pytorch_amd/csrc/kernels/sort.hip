@@ -1,5 +1,5 @@
 // Own stable LSD radix sort of (id, row) pairs on gfx950: 8-bit digits, ceil(bits / 8) passes.  The deterministic
-// embedding backward (embed.hip, f32_ops.hip) sorts the token rows by word / position / type id with it.
+// embedding backward (embed.hip, f32_embed.hip) sorts the token rows by word / position / type id with it.
 #include "hq_common.h"
 #include "hq_kernels.h"
 

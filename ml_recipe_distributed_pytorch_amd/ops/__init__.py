@@ -7,7 +7,7 @@
 * CPU tensors → ``ops.reference`` (pure PyTorch, fp32), which is also the numerics oracle.
 * fp32 GPU tensors (``--precision fp32``, the reference's Apex-off mode) → ``ops.f32``: every GEMM-shaped product
   on the own exact-f32 MFMA kernel (``gemm_f32.hip``), the row-wise / elementwise parts and the flash attention on
-  the own fp32 kernels (``f32_ops.hip``).
+  the own fp32 kernels (``f32_embed.hip``, ``f32_norm.hip``, ``f32_rowops.hip``, ``f32_attention.hip``).
 """
 from __future__ import annotations
 

@@ -5,7 +5,7 @@ fp32, ``/root/reference/modules/model/trainer/trainer.py:23-32,128-133,200-204``
 Every GEMM-shaped FLOP runs on the own exact-f32 MFMA kernel (``csrc/kernels/gemm_f32.hip``,
 ``v_mfma_f32_32x32x2_f32``: a k-ordered fp32 fma chain, no reduced-precision inputs): the encoder projections
 (forward, dgrad and weight gradient, addressed as strided views — no transposed copies).  The attention is a
-flash-style fp32 kernel (``csrc/kernels/f32_ops.hip``: scores recomputed per 32-key tile in registers, online
+flash-style fp32 kernel (``csrc/kernels/f32_attention.hip``: scores recomputed per 32-key tile in registers, online
 softmax forward, LSE backward — no [B, nh, L, L] tensor at any length), and the row-wise / elementwise parts
 (embedding gathers + LayerNorm, residual + dropout + LayerNorm, GELU, the bias-gradient column sums) are own fp32
 kernels too, with the dropout masks of ``ops.rng`` — so the fp32 GPU model reproduces the CPU oracle op for op.
@@ -89,7 +89,7 @@ def linear_wgrad(dy, x, g_w, g_b, accumulate: bool):
         kernels().f32_colsum(dy, g_b, bool(accumulate))
 
 
-# ------------------------------------------------------------------------------------ row-wise ops (f32_ops.hip)
+# ------------------------------------------------------------------------------------ row-wise ops (f32_*.hip)
 def embed_fwd(ids, pos_ids, type_ids, w_word, w_pos, w_type, gamma, beta, eps, p, seed, opid):
     return tuple(kernels().f32_embed_fwd(ids.contiguous(), pos_ids.contiguous(), type_ids.contiguous(),
                                          w_word.contiguous(), w_pos.contiguous(), w_type.contiguous(), gamma.contiguous(),

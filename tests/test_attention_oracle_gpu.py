@@ -1,4 +1,4 @@
-"""Attention kernels (csrc/kernels/attention.hip, the fp32 flash attention of f32_ops.hip) against a float64 oracle
+"""Attention kernels (csrc/kernels/attention.hip, the fp32 flash attention of f32_attention.hip) against a float64 oracle
 with per-row error bounds, and exact probes of every (query, key) term.
 
 Oracle (tests/attn_oracle.py): float64 forward and backward from the bf16 inputs; its own lse, ctx and δ; the
@@ -420,7 +420,7 @@ def test_fp8_forward_ctx8_away_from_384(cuda, L, p):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", F32_CASES, ids=_id)
 def test_f32_attention_against_oracle(cuda, case):
-    """The fp32 flash attention (f32_ops.hip) in the same per-row form with u = 2⁻²⁴."""
+    """The fp32 flash attention (f32_attention.hip) in the same per-row form with u = 2⁻²⁴."""
     B, L, nh, p = case
     (qkv, kb, dctx), orc = ao.f32_case(*case)
     k = _native.kernels()

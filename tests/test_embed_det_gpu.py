@@ -2,7 +2,8 @@
 position and (> 2 types) type tables, and the bf16 kernels' deterministic-positions / sorted-type modes.
 
 Every table row is summed in a documented order (stated above embed.hip embed_word_kernel; the fp32 pair of kernels
-is f32_ops.hip f32_embed_run_kernel): tokens sorted stably by the table's key, the sorted list cut into chunks of ``embed_run_chunk()`` positions; the rows
+is f32_embed.hip f32_embed_run_kernel): tokens sorted stably by the table's
+key, the sorted list cut into chunks of ``embed_run_chunk()`` positions; the rows
 of one key inside one chunk (a piece) are summed from zero in token order, the pieces of a run that crosses chunks are
 added in chunk order, and accumulate adds the existing row last.  The tests check that order bit for bit, the values
 against the fp32 oracle, run-to-run equality, and whole training steps."""
@@ -181,7 +182,8 @@ def _documented_sum(keys, dx, init, pad, accumulate, CH):
 
 @pytest.mark.parametrize("accumulate", [False, True])
 @pytest.mark.parametrize("H", [128, 768])
-@pytest.mark.parametrize("prec,table", [("fp32", "word"), ("fp32", "pos"), ("bf16", "pos")])
+@pytest.mark.parametrize("prec,table", [("fp32", "word"), ("fp32", "pos"), ("fp32", "type"), ("bf16", "word"),
+                                        ("bf16", "pos"), ("bf16", "type")])
 def test_bitwise_documented_order(cuda, prec, table, H, accumulate):
     """Run A gives every token a key of its own, so each stored row is that token's dx; run B gives the tokens of a
     group the group's key.  The table rows of a group are equal, so both runs see the same x, dy, statistics and
@@ -200,10 +202,13 @@ def test_bitwise_documented_order(cuda, prec, table, H, accumulate):
         tab = _bf(tab).float()
     if table == "word":
         c.ww, c.V = tab, NKB + T_
-    else:
+    elif table == "pos":
         c.wp, c.P, c.pad_pos = tab, NKB + T_, PAD
-    field = "ids" if table == "word" else "pids"
-    ti = 0 if table == "word" else 1
+    else:   # more than 2 types: the type rows come from the sorted runs too, and no type is skipped
+        c.wt, c.NTY = tab, NKB + T_
+    field = {"word": "ids", "pos": "pids", "type": "tids"}[table]
+    ti = NAMES.index(table)
+    pad = -1 if table == "type" else PAD
     # run A: fresh tables, the statistics of run B's forward (equal x), one row per token
     setattr(c, field, keys_b)
     init_b = _init(c, accumulate)
@@ -212,7 +217,7 @@ def test_bitwise_documented_order(cuda, prec, table, H, accumulate):
     out_a, m_a, rs_a, _, _ = _run(k, cuda, c, prec, _init(c, False), False)
     assert torch.equal(m, m_a) and torch.equal(rs, rs_a), "both runs must see the same x"
     dx = out_a[ti][NKB:]
-    want = _documented_sum(keys_b, dx, init_b[ti], PAD, accumulate, CH)
+    want = _documented_sum(keys_b, dx, init_b[ti], pad, accumulate, CH)
     assert int((keys_b == 4).sum()) > 4 * CH
     assert torch.equal(out_b[ti], want), (
         f"{prec} {table} rows differ from the documented order in "

@@ -1,4 +1,4 @@
-"""The native fp32 row-wise ops and flash attention of ``--precision fp32`` (csrc/kernels/f32_ops.hip) against the
+"""The native fp32 row-wise ops and flash attention of ``--precision fp32`` (csrc/kernels/f32_*.hip) against the
 fp32 CPU oracle (ops/reference.py) — same inputs, same dropout masks (ops.rng counter hash)."""
 import pytest
 import torch

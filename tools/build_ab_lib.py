@@ -10,7 +10,9 @@ A file is overlaid whole, so REV must define the same functions in it as the tre
 norm.hip (into norm / embed / sort / rowops.hip, the span head into heads.hip) and moved the fp8 quantisers and amax
 folds from gemm_fp8.hip to fp8.hip, name every file the subject moved between (and include/hq_kernels.h), or the
 link has duplicate or missing hq_* symbols; a subject whose file does not exist at REV (embed / sort / rowops.hip)
-cannot be overlaid from before that commit — build that revision whole in a worktree instead.
+cannot be overlaid from before that commit — build that revision whole in a worktree instead.  Likewise across the
+commit that split the fp32 ops file into f32_embed / f32_norm / f32_rowops / f32_attention.hip: from before it, build the whole revision in a worktree
+(AB_DIR still picks where the library goes).
 """
 import os
 import shutil
