@@ -1169,6 +1169,10 @@ PYBIND11_MODULE(_hq_kernels, m) {
   m.def("gemm_nt_part_rows", [](int64_t M, int64_t N, int64_t K) {
     return (int64_t)hq_gemm_nt_part_rows((int)M, (int)N, (int)K);
   });
+  // floats of the split-K workspace gemm_nt allocates for this shape and epilogue: ksplit·M·N, or 0 (no split)
+  m.def("gemm_nt_ws_floats", [](int64_t M, int64_t N, int64_t K, int64_t epi) {
+    return (int64_t)hq_gemm_nt_ws_floats((int)M, (int)N, (int)K, (int)epi);
+  });
   m.def("gemm_set_variant", [](int64_t v) { hq_gemm_set_variant((int)v); });
   m.def("gemm_set_store_policy", [](int64_t v) { hq_gemm_set_store_policy((int)v); });
   m.def("gemm_set_stagger", [](int64_t v) { hq_gemm_set_stagger((int)v); });

@@ -274,6 +274,8 @@ def test_gemm_nt_split_k_low_fill(cuda, M, N, K, variant):
         pytest.skip("split-K lives in the 128²-tile kernel")
     k = _native.kernels()
     assert k.gemm_nt_supported(M, N, K) == 1
+    for epi in (EPI_NONE, EPI_BIAS, EPI_RESID):
+        assert k.gemm_nt_ws_floats(M, N, K, epi) > 0, "the shape no longer splits K: this test would test nothing"
     g = torch.Generator(device=cuda).manual_seed(M + K)
     A = (torch.randn(M, K, device=cuda, generator=g) * 0.5).bfloat16()
     B = (torch.randn(N, K, device=cuda, generator=g) * 0.1).bfloat16()

@@ -1,0 +1,576 @@
+"""bf16 NT GEMM (csrc/kernels/gemm.hip, the shared epilogue of csrc/include/hq_gemm_epi.h) and the TN weight gradient
+(gemm_tn.hip) against a float64 oracle with per-element bounds, and exact integer probes of every dispatch path.
+
+tests/gemm_oracle.py holds the oracle, the bounds, the fp32 emulation of the kernels' roundings with its planted
+mistakes, and the integer probes; its docstring derives the bounds and names the two rounding orders.
+
+Without a GPU (the proof that the bounds have teeth):
+  * the oracle equals a plain float64 computation of each epilogue written out here;
+  * the emulation, in both rounding orders, and the plain fp32 reference lie inside every bound at every bound-test
+    shape and input set (largest reference-to-bound ratio 0.9999: a bf16 tie with a negligible E_acc; on an MI355X
+    the kernels reach 0.9999 as well, 0.978 to 0.997 on the unit and small sets);
+  * E_Φ, the sup error of the header's Φ formula against erfc, is measured (1.096e-5) and is below the 1.3e-5 the
+    header documents; the formula's constants are read from the header text;
+  * every planted mistake is rejected: a whole-matrix mistake puts at least 1 % of the elements of some output of
+    every epilogue it touches outside the bound, at every shape; the flipped keep bit exactly its one element; the
+    two column-partial mistakes at least 1 % of the columns of the planted part row and nothing else;
+  * the integer probes have values bf16 must round, ties among them, and column sums exact in any order, at every
+    probe shape.
+
+On the GPU:
+  * bound tests: every element of C and P and every row of part, every epilogue, every variant, four shapes with
+    K <= 256, three input sets;
+  * exact probes (torch.equal): each test restates the dispatch rule of launch_epi from the CU count and asserts what
+    the bindings can show of it (gemm_nt_supported, gemm_nt_part_rows, gemm_nt_ws_floats) before it runs;
+  * guards: C and P are views of canary-filled tensors, part has a canary row: nothing past M or past the part rows
+    changes, in every run of this file;
+  * gemm_tn: exact integer probes over split counts, variants, accumulation and the fused bias gradient.
+"""
+import contextlib
+import functools
+import math
+import os
+import re
+
+import pytest
+import torch
+
+import gemm_oracle as go
+from gemm_oracle import (COL_PARTIALS, EPI_BDR, EPI_BIAS, EPI_DGELU, EPI_DMUL, EPI_GELU, EPI_GELUD, EPI_NAMES,
+                         EPI_NONE, EPI_RESID, EPIS, SPLITTABLE, WRITES_P)
+from ml_recipe_distributed_pytorch_amd import _native
+
+HT = 1 << 16          # gemm_set_stagger: the half-tile tail bit (on by default)
+CANARY = 7.0
+GUARD_ROWS = 64
+NCU_MI355X = 256
+
+
+# ------------------------------------------------------------------------------------- the dispatch, restated
+def dispatch(M, N, K, epi, variant, ncu, stagger=HT, sched=0):
+    """hq_gemm_nt_supported, nts_ksplit, half_tile_tail and launch_epi of gemm.hip, restated: which kernel serves
+    (M, N, K, epi) under gemm_set_variant(variant) on ``ncu`` CUs.  bn: what gemm_nt_supported returns."""
+    assert N % 128 == 0 and K % 64 == 0 and K >= 64
+    big = (256 if N % 256 == 0 else 128) if M % 256 == 0 else 0
+    if variant == 4 or not big:
+        bn = 1
+    elif variant:
+        bn = big
+    else:                                            # auto: the 256-row kernels if they fill >= 80 % of their waves
+        tiles = (M // 256) * (N // big)
+        bn = big if tiles * 5 >= -(-tiles // ncu) * ncu * 4 else 1
+    d = {"bn": bn, "ksplit": 1, "tail": False, "grouped": False, "dynamic": False}
+    if bn == 1:
+        tiles, nk, ks = -(-M // 128) * (N // 128), K // 64, 1
+        if epi in SPLITTABLE:
+            ks = 2 * ncu // tiles if 2 * tiles <= ncu else 1
+            ks = max(1, min(ks, 4, nk // 8))
+        d.update(kernel="vS", ksplit=ks, part_rows=-(-M // 128), M_block=128)
+        return d
+    grid = (M // 256) * (N // bn)
+    rt = grid % ncu
+    tail = bool(stagger & HT) and epi not in COL_PARTIALS and rt > 0 and 2 * rt <= ncu and grid > ncu
+    d.update(part_rows=M // 256, M_block=256, grid=grid)
+    if bn == 256 and K >= 128 and (variant == 3 or (variant == 0 and (K <= 2304 or tail))):
+        d.update(kernel="v3", tail=tail, dynamic=bool(sched) and grid > 2 * min(grid, ncu))
+    elif bn == 256 and K >= 128 and variant in (0, 2, 3):
+        grouped = N // 256 >= 16
+        d.update(kernel="v2", grouped=grouped, tail=tail and not grouped)
+    else:
+        d.update(kernel="v1")
+    return d
+
+
+def persistent_shapes(ncu):
+    """(tail N = 4096, tail N = 2048, dynamic): M of the persistent-kernel probes on ``ncu`` CUs: ncu + 16 tiles of
+    256² (one wave and a tail of 16 <= ncu / 2) at 16 and at 8 tiles per row, 2·ncu + 16 tiles (more than twice the
+    workgroups, the ticket schedule's condition) at 16 per row.  256 CUs: 256·17, 256·34, 256·33."""
+    return 256 * -(-(ncu + 16) // 16), 256 * -(-(ncu + 16) // 8), 256 * -(-(2 * ncu + 16) // 16)
+
+
+def test_dispatch_restated_for_the_probe_shapes():
+    """The shapes of the exact probes reach the mechanism they are named for on 256 CUs (the GPU tests assert the
+    same from the device's CU count, and what the bindings show of the rule)."""
+    n = NCU_MI355X
+    assert [dispatch(256, 256, 128, EPI_NONE, v, n)["kernel"] for v in range(5)] == ["vS", "v1", "v2", "v3", "vS"]
+    assert dispatch(256, 128, 64, EPI_NONE, 1, n) == dispatch(256, 128, 64, EPI_NONE, 3, n)
+    assert dispatch(256, 128, 64, EPI_NONE, 1, n)["kernel"] == "v1" and dispatch(256, 128, 64, EPI_NONE, 1, n)["bn"] == 128
+    assert dispatch(512, 384, 192, EPI_NONE, 1, n)["bn"] == 128
+    for shape in ((100, 128, 64), (129, 128, 128), (1268, 256, 192), (1268, 256, 256)):
+        assert all(dispatch(*shape, EPI_DMUL, v, n)["kernel"] == "vS" for v in range(5))
+    for epi in SPLITTABLE:
+        assert dispatch(200, 128, 1600, epi, 0, n)["ksplit"] == 3 and dispatch(1000, 768, 2048, epi, 0, n)["ksplit"] == 4
+        assert dispatch(256, 256, 3072, epi, 4, n)["ksplit"] == 4
+    assert [(s * 25 // 3, (s + 1) * 25 // 3) for s in range(3)] == [(0, 8), (8, 16), (16, 25)]   # 8 / 8 / 9 K-tiles
+    assert dispatch(200, 128, 1600, EPI_DMUL, 0, n)["ksplit"] == 1
+    m16, m8, mdyn = persistent_shapes(n)
+    assert (m16, m8, mdyn) == (256 * 17, 256 * 34, 256 * 33)
+    d = dispatch(m16, 4096, 128, EPI_BIAS, 3, n)
+    assert d["kernel"] == "v3" and d["tail"] and d["grid"] == 272 and not dispatch(m16, 4096, 128, EPI_BIAS, 3, n, 0)["tail"]
+    assert not dispatch(m16, 4096, 128, EPI_DMUL, 3, n)["tail"]
+    # auto does not take the 256-row kernels for a last wave this empty (272 of 512 slots): it runs vS
+    assert dispatch(m16, 4096, 128, EPI_BIAS, 0, n)["kernel"] == "vS"
+    d = dispatch(m16, 4096, 128, EPI_BIAS, 2, n)
+    assert d["kernel"] == "v2" and d["grouped"] and not d["tail"]
+    d = dispatch(m8, 2048, 128, EPI_BIAS, 2, n)
+    assert d["kernel"] == "v2" and not d["grouped"] and d["tail"] and d["grid"] == 272
+    d = dispatch(mdyn, 4096, 128, EPI_BIAS, 3, n, sched=1)
+    assert d["kernel"] == "v3" and d["dynamic"] and d["grid"] == 528 and not dispatch(mdyn, 4096, 128, EPI_BIAS, 3, n)["dynamic"]
+    assert [dispatch(256, 256, 3072, EPI_GELU, v, n)["kernel"] for v in range(5)] == ["vS", "v1", "v2", "v3", "vS"]
+
+
+# -------------------------------------------------------------------------------------------------- CPU tests
+def _phi_erf(x):
+    return 0.5 * (1.0 + torch.erf(x / math.sqrt(2.0)))
+
+
+def test_oracle_equals_plain_float64():
+    """Each epilogue written out plainly in float64 (Φ through erf, where the oracle uses erfc)."""
+    M, N, K = 100, 128, 64
+    inp = go.cpu_inputs(M, N, K, "small")
+    A, B = inp["A"].double(), inp["B"].double()
+    bias, resid, pre, gd = inp["bias"].double(), inp["resid"].double(), inp["pre"].double(), inp["gd"].double()
+    acc = torch.einsum("mk,nk->mn", A, B)
+    x = acc + bias[None, :]
+    pdf = lambda t: torch.exp(-t * t / 2) / math.sqrt(2 * math.pi)
+    keep = go.rng.keep_mask_from_index(torch.arange(M)[:, None] * N + torch.arange(N)[None, :], go.SEED, go.OPID,
+                                       go.P_DROP).double()
+    dg = acc * (_phi_erf(pre) + pre * pdf(pre))
+    plain = {EPI_NONE: (acc, None), EPI_BIAS: (x, None), EPI_GELU: (x * _phi_erf(x), x),
+             EPI_GELUD: (x * _phi_erf(x), _phi_erf(x) + x * pdf(x)), EPI_DGELU: (dg, None), EPI_DMUL: (acc * gd, None),
+             EPI_RESID: (acc + resid, None), EPI_BDR: (x * keep / (1.0 - round(go.P_DROP * 65536) / 65536) + resid, None)}
+    for epi in EPIS:
+        o = go.oracle(inp["A"], inp["B"], epi, M_block=64, **go.epi_args(inp, epi))
+        C, P = plain[epi]
+        torch.testing.assert_close(o["C"], C, rtol=1e-12, atol=1e-13)
+        assert (o["P"] is None) == (P is None)
+        if P is not None:
+            torch.testing.assert_close(o["P"], P, rtol=1e-12, atol=1e-13)
+        assert (o["part"] is not None) == (epi in COL_PARTIALS)
+        if epi in COL_PARTIALS:
+            assert o["part"].shape == (2, N)
+            torch.testing.assert_close(o["part"][0], C[:64].sum(0), rtol=1e-12, atol=1e-13)
+            torch.testing.assert_close(o["part"][1], C[64:].sum(0), rtol=1e-12, atol=1e-13)      # rows 64..99 only
+    S = torch.einsum("mk,nk->mn", A.abs(), B.abs())
+    torch.testing.assert_close(go.oracle(inp["A"], inp["B"], EPI_NONE)["S"], S, rtol=1e-12, atol=0)
+
+
+def test_half_ulp_is_exact():
+    hu = go.half_ulp_bf16
+    x = torch.tensor([1.0, 1.99, 2.0, -3.0, 0.75, 2.0 ** -126, 2.0 ** -130, 0.0], dtype=torch.float64)
+    exp = [2.0 ** -8, 2.0 ** -8, 2.0 ** -7, 2.0 ** -7, 2.0 ** -9, 2.0 ** -134, 2.0 ** -134, 2.0 ** -134]
+    assert hu(x).tolist() == exp
+    # RNE stays within it and reaches it; a flat 2⁻⁹·|x| (the unit roundoff of bf16 is 2⁻⁸) fails RNE itself
+    v = torch.arange(1.0, 4.0, 2.0 ** -12, dtype=torch.float64).float()      # holds the ties 1 + (2j + 1)·2⁻⁸
+    err = (v.bfloat16().double() - v.double()).abs()
+    assert bool((err <= hu(v.double())).all()) and bool((err == hu(v.double())).any())
+    assert float((err / (2.0 ** -9 * v.double())).max()) > 1.9
+
+
+def test_phi_formula_error():
+    """E_Φ: sup |Φ_formula − Φ| on a dense grid over [−12, 12], the formula evaluated in float64 (and in fp32, as
+    the emulation does, against the documented bound and the E_PHI the bounds use)."""
+    x = torch.linspace(-12.0, 12.0, 2_400_001, dtype=torch.float64)
+    e64 = float((go.normal_cdf_pdf(x)[0] - go.phi64(x)).abs().max())
+    x32 = x.float()
+    e32 = float((go.normal_cdf_pdf(x32)[0].double() - go.phi64(x32.double())).abs().max())
+    print(f"[gemm-oracle] E_PHI float64 {e64:.4e}  fp32 {e32:.4e}")
+    assert e64 <= 1.3e-5 and e32 <= 1.3e-5                       # hq_common.h: |Φ err| < 1.3e-5
+    assert 0.99 * go.E_PHI_MEASURED <= e64 <= go.E_PHI_MEASURED and e32 <= go.E_PHI
+    assert go.E_PHI == 1.1 * go.E_PHI_MEASURED
+    # absolute, not relative: on (−8, −5) gelu by the formula is many half ulps from erf-GELU, and tiny
+    t = torch.linspace(-8.0, -5.0, 30001, dtype=torch.float64)
+    d = (t * go.normal_cdf_pdf(t)[0] - go.gelu64(t)).abs()
+    assert float((d / go.half_ulp_bf16(go.gelu64(t))).max()) > 10.0 and float(d.max()) < 2.6e-5
+
+
+def test_constants_are_those_of_the_header():
+    """The Φ formula's constants, and the Lipschitz constants of the bounds."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    with open(os.path.join(root, "ml_recipe_distributed_pytorch_amd", "csrc", "include", "hq_common.h")) as f:
+        text = f.read()
+    body = text[text.index("void hq_normal_cdf_pdf("):text.index("float hq_gelu(float x)")]
+    lits = [float(s) for s in re.findall(r"(-?\d+\.\d+)f", body)]
+    assert lits == [go.C_P, go.C_A3, go.C_A2, go.C_A1, go.C_EXP2, go.C_PDF], lits
+    assert "fmaf(fmaf(0.3739278f, t, -0.0479399f), t, 0.1740121f) * t" in body and "x >= 0.f ? 1.f - q : q" in body
+    assert abs(go.C_EXP2 + 0.5 / math.log(2.0)) < 1e-15 and abs(go.C_PDF - 1 / math.sqrt(2 * math.pi)) < 1e-15
+    x = torch.linspace(-12.0, 12.0, 240001, dtype=torch.float64)
+    assert 1.128 < float(go.gelu_grad64(x).abs().max()) <= go.L_GELU
+    g2 = go.pdf64(x) * (2.0 - x * x)                             # gelu'' = φ·(2 − x²)
+    assert 0.797 < float(g2.abs().max()) <= go.L_GELU_GRAD
+
+
+def _m_blocks(M, epi):
+    """The column-partial block heights a kernel can have at this M."""
+    if epi not in COL_PARTIALS:
+        return (256,)
+    return (256, 128) if M % 256 == 0 else (128,)
+
+
+def test_emulation_and_reference_lie_inside_every_bound():
+    worst = {"reference": 0.0, "staged": 0.0, "splitk": 0.0}
+    outside = []
+    for shape in go.BOUND_SHAPES:
+        for s in go.INPUT_SETS:
+            inp = go.cpu_inputs(*shape, s)
+            A, B = inp["A"], inp["B"]
+            for epi in EPIS:
+                kw = go.epi_args(inp, epi)
+                for mb in _m_blocks(shape[0], epi):
+                    o = go.oracle(A, B, epi, M_block=mb, **kw)
+                    b = go.bounds(o)
+                    runs = [("reference", go.fp32_reference(A, B, epi, M_block=mb, **kw)),
+                            ("staged", go.emulate(A, B, epi, M_block=mb, **kw))]
+                    if epi in SPLITTABLE:
+                        runs.append(("splitk", go.emulate(A, B, epi, M_block=mb, order="splitk", **kw)))
+                    for name, got in runs:
+                        for out, bad, tot, ratio, at in go.check(got, o, b):
+                            worst[name] = max(worst[name], ratio)
+                            if bad:
+                                outside.append((shape, s, EPI_NAMES[epi], name, out, bad, tot, ratio, at))
+    print("[gemm-oracle] largest |x − oracle| / bound: " + "  ".join(f"{n} {w:.4f}" for n, w in worst.items()))
+    assert not outside, outside
+    assert 0.9 < worst["reference"] <= 1.0 and 0.9 < worst["staged"] <= 1.0      # and the bounds are not slack
+
+
+WHOLE_MATRIX = ("trunc_round", "drop_last_k", "gain_1.01", "bias_next_col", "resid_next_row", "no_keep_scale",
+                "dgelu_uses_gelu", "cdf_zero_below_-3")
+REJECT_SHARE = 0.01
+
+
+@pytest.mark.parametrize("mutant", go.MUTANTS)
+def test_mutants_are_rejected(mutant):
+    """A whole-matrix mistake: at every bound-test shape, every epilogue whose emulated output it changes has an
+    output with at least REJECT_SHARE = 1 % of its elements outside the bound.  keep_bit_flip: exactly the planted
+    element of C.  The column-partial mistakes: C unchanged and inside, at least 1 % of the columns of the planted
+    (last) part row outside, no other part row."""
+    touched = 0
+    for shape in go.BOUND_SHAPES:
+        M = shape[0]
+        inp = go.cpu_inputs(*shape, "small")
+        A, B = inp["A"], inp["B"]
+        for epi in EPIS:
+            kw = go.epi_args(inp, epi)
+            for mb in _m_blocks(M, epi):
+                base = go.emulate(A, B, epi, M_block=mb, **kw)
+                got = go.emulate(A, B, epi, M_block=mb, mutant=mutant, **kw)
+                if all(torch.equal(got[n], base[n]) for n in ("C", "P", "part") if got[n] is not None):
+                    continue
+                touched += 1
+                o = go.oracle(A, B, epi, M_block=mb, **kw)
+                b = go.bounds(o)
+                res = {n: (bad, tot, at) for n, bad, tot, _, at in go.check(got, o, b)}
+                what = (mutant, shape, EPI_NAMES[epi], mb, res)
+                if mutant in WHOLE_MATRIX:
+                    assert max(bad / tot for bad, tot, _ in res.values()) >= REJECT_SHARE, what
+                elif mutant == "keep_bit_flip":
+                    assert epi == EPI_BDR and res["C"][0] == 1, what
+                    assert res["C"][2] == (go.FLIP_AT[0] % M, go.FLIP_AT[1] % shape[1]), what
+                else:
+                    assert epi in COL_PARTIALS and res["C"][0] == 0 and torch.equal(got["C"], base["C"]), what
+                    out = (got["part"] - o["part"]).abs() > b["part"]
+                    assert not bool(out[:-1].any()), what
+                    assert float(out[-1].double().mean()) >= REJECT_SHARE, what
+    assert touched >= (2 if mutant == "part_sums_rows_past_M" else len(go.BOUND_SHAPES)), (mutant, touched)
+
+
+# the exact probes' shapes (256 CUs), for the CPU check of the generator's conditions
+PROBE_SHAPES = [(256, 256, 128), (256, 128, 64), (512, 384, 192), (100, 128, 64), (129, 128, 128), (1268, 256, 192),
+                (200, 128, 1600), (1000, 768, 2048), (256, 256, 3072)]
+BIG_PROBE_SHAPES = [(256 * 17, 4096, 128), (256 * 34, 2048, 128), (256 * 33, 4096, 128)]
+
+
+@pytest.mark.parametrize("M,N,K", PROBE_SHAPES + BIG_PROBE_SHAPES)
+def test_int_probe_conditions(M, N, K):
+    """int_probe asserts its own conditions (values bf16 must round, exact ties, column sums exact in any order); here
+    also: the two rounding orders differ somewhere for RESID, and the expected values are integers bf16 holds."""
+    if (M, N, K) in BIG_PROBE_SHAPES:
+        M = 512                                      # the same generator and K; the conditions are per element
+    pr = go.int_probe(M, N, K)
+    st = go.probe_expected(pr, EPI_RESID, "staged")["C"]
+    sk = go.probe_expected(pr, EPI_RESID, "splitk")["C"]
+    assert not torch.equal(st, sk)
+    for epi in EPIS:
+        e = go.probe_expected(pr, epi, M_block=128)
+        assert e["C"].dtype == torch.bfloat16 and bool(torch.isfinite(e["C"].float()).all())
+        assert (e["P"] is not None) == (epi in WRITES_P) and (e["part"] is not None) == (epi in COL_PARTIALS)
+    keep = go.keep_of(M, N, pr["p"], pr["seed"], pr["opid"], "cpu")[0]
+    assert 0.4 < float(keep.mean()) < 0.6
+
+
+# -------------------------------------------------------------------------------------------------- GPU side
+@contextlib.contextmanager
+def gemm_mode(k, variant=0, stagger=HT, sched=None):
+    """Select the kernel variant, the v3 flag word and the tile schedule; put the defaults (variant 0, the half-tile
+    tail on) and the previous schedule back."""
+    prev = k.gemm_get_sched()
+    try:
+        k.gemm_set_variant(variant)
+        k.gemm_set_stagger(stagger)
+        if sched is not None:
+            k.gemm_set_sched(sched)
+        yield
+    finally:
+        k.gemm_set_variant(0)
+        k.gemm_set_stagger(HT)
+        k.gemm_set_sched(prev)
+
+
+def _ncu():
+    return torch.cuda.get_device_properties(0).multi_processor_count
+
+
+def _assert_dispatch(k, M, N, K, epi, d):
+    """What the bindings show of the dispatch, against the restated rule."""
+    assert k.gemm_nt_supported(M, N, K) == d["bn"], (M, N, K, d)
+    assert k.gemm_nt_part_rows(M, N, K) == d["part_rows"], (M, N, K, d)
+    assert k.gemm_nt_ws_floats(M, N, K, epi) == (d["ksplit"] * M * N if d["ksplit"] > 1 else 0), (M, N, K, epi, d)
+
+
+def _run(k, A, B, epi, kw, K):
+    """gemm_nt into canary-guarded outputs: C and P are the first M rows of tensors with GUARD_ROWS more, part has
+    one row more than gemm_nt_part_rows; nothing past them may change."""
+    M, N, dev = A.shape[0], B.shape[0], A.device
+    kk = dict(kw)
+    big = {"out": torch.full((M + GUARD_ROWS, N), CANARY, device=dev, dtype=torch.bfloat16)}
+    kk["out"] = big["out"][:M]
+    if epi in WRITES_P:
+        big["pre"] = torch.full((M + GUARD_ROWS, N), CANARY, device=dev, dtype=torch.bfloat16)
+        kk["pre"] = big["pre"][:M]
+    rows = 0
+    if epi in COL_PARTIALS:
+        rows = k.gemm_nt_part_rows(M, N, K)
+        big["part"] = torch.full((rows + 1, N), CANARY, device=dev)
+        kk["part"] = big["part"][:rows]
+    C = k.gemm_nt(A, B, epi, **kk)
+    torch.cuda.synchronize()
+    assert C.data_ptr() == big["out"].data_ptr()
+    for n, t in big.items():
+        past = t[rows:] if n == "part" else t[M:]
+        assert bool((past == CANARY).all()), f"{EPI_NAMES[epi]}: {n} was written past its rows"
+    return {"C": kk["out"], "P": kk.get("pre") if epi in WRITES_P else None, "part": kk.get("part")}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("input_set", go.INPUT_SETS)
+@pytest.mark.parametrize("M,N,K", go.BOUND_SHAPES)
+def test_every_element_within_its_bound(cuda, M, N, K, input_set):
+    """Every element of C and P and every row of part within its own bound (gemm_oracle.bounds), every epilogue,
+    every variant: the 256-row kernels where M % 256 == 0 (v1 alone where N % 256 != 0), vS everywhere."""
+    k = _native.kernels()
+    ncu = _ncu()
+    inp = go.make_inputs(M, N, K, input_set, device=cuda)
+    A, B = inp["A"], inp["B"]
+    orc = {}
+    outside, worst, kernels = [], 0.0, set()
+    for variant in ((0, 1, 2, 3, 4) if M % 256 == 0 else (0, 4)):
+        with gemm_mode(k, variant):
+            for epi in EPIS:
+                d = dispatch(M, N, K, epi, variant, ncu)
+                _assert_dispatch(k, M, N, K, epi, d)
+                assert d["ksplit"] == 1
+                kernels.add(d["kernel"])
+                kw = go.epi_args(inp, epi)
+                key = (epi, d["M_block"] if epi in COL_PARTIALS else 0)
+                if key not in orc:
+                    o = go.oracle(A, B, epi, M_block=d["M_block"], **kw)
+                    orc[key] = (o, go.bounds(o))
+                o, b = orc[key]
+                got = _run(k, A, B, epi, kw, K)
+                for out, bad, tot, ratio, at in go.check(got, o, b):
+                    worst = max(worst, ratio)
+                    if bad:
+                        outside.append((variant, d["kernel"], EPI_NAMES[epi], out, bad, tot, ratio, at))
+    print(f"[gemm-oracle] {M}x{N}x{K} {input_set}: largest |kernel − oracle| / bound {worst:.4f} ({sorted(kernels)})")
+    assert kernels == ({"vS", "v1", "v2", "v3"} if (M % 256 == 0 and N % 256 == 0) else
+                       {"vS", "v1"} if M % 256 == 0 else {"vS"})
+    assert not outside, outside
+
+
+@functools.lru_cache(maxsize=2)
+def _gpu_probe(M, N, K):
+    return go.int_probe(M, N, K, device="cuda")
+
+
+def _probe(k, M, N, K, variant, ncu, want=None, stagger=HT, sched=None, epis=EPIS):
+    """Every epilogue in ``epis`` on the integer probe of this shape, bitwise: C, P and every part row.  ``want``:
+    what the restated dispatch must say for every epilogue (for the epilogues in its 'epis', if given).  Returns
+    {epi: dispatch}."""
+    pr = _gpu_probe(M, N, K)
+    seen, wrong = {}, []
+    with gemm_mode(k, variant, stagger, sched):
+        eff_sched = k.gemm_get_sched()
+        for epi in epis:
+            d = dispatch(M, N, K, epi, variant, ncu, stagger, eff_sched)
+            _assert_dispatch(k, M, N, K, epi, d)
+            seen[epi] = d
+            exp = go.probe_expected(pr, epi, "splitk" if d["ksplit"] > 1 else "staged", d["M_block"])
+            got = _run(k, pr["A"], pr["B"], epi, go.probe_args(pr, epi), K)
+            for n in ("C", "P", "part"):
+                assert (exp[n] is None) == (got[n] is None)
+                if exp[n] is not None and not torch.equal(got[n], exp[n]):
+                    ne = (got[n].double() != exp[n].double()).nonzero()
+                    wrong.append((EPI_NAMES[epi], d["kernel"], n, len(ne), ne[0].tolist(), ne[-1].tolist()))
+    assert not wrong, f"(epilogue, kernel, output, elements wrong, first, last): {wrong}"
+    if want:
+        for epi, d in seen.items():
+            assert all(d[f] == v for f, v in want.items()), (EPI_NAMES[epi], d, want)
+    return seen
+
+
+SMALL_PROBES = [((256, 256, 128), 0, "vS"), ((256, 256, 128), 1, "v1"), ((256, 256, 128), 2, "v2"),
+                ((256, 256, 128), 3, "v3"), ((256, 256, 128), 4, "vS"),
+                ((256, 128, 64), 1, "v1"), ((256, 128, 64), 3, "v1"), ((256, 128, 64), 0, "vS"),      # K = 64, 128-wide v1
+                ((512, 384, 192), 1, "v1"), ((512, 384, 192), 0, "vS"), ((512, 384, 192), 4, "vS"),   # N % 256 != 0
+                ((100, 128, 64), 0, "vS"), ((100, 128, 64), 4, "vS"), ((129, 128, 128), 0, "vS"),     # M tails
+                ((129, 128, 128), 4, "vS"), ((1268, 256, 192), 0, "vS"), ((1268, 256, 192), 4, "vS")]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape,variant,kernel", SMALL_PROBES,
+                         ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_exact_every_family_at_its_smallest_shapes(cuda, shape, variant, kernel):
+    """Each kernel family at the smallest shape it serves, the 128-wide v1 at K = 64, three K-tiles with
+    N % 256 != 0, and the vS M tails (100: one partial tile; 129: a tile of one row; 1268: M % 128 = 116); C, P and
+    part bitwise, rows past M and past the part rows untouched."""
+    M, N, K = shape
+    seen = _probe(_native.kernels(), M, N, K, variant, _ncu(), want={"kernel": kernel, "ksplit": 1})
+    if kernel == "vS":
+        assert seen[EPI_DMUL]["part_rows"] == -(-M // 128)
+    if (M, N, K) == (256, 128, 64):
+        assert kernel == "vS" or seen[EPI_NONE]["bn"] == 128
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant", [0, 4])
+@pytest.mark.parametrize("M,N,K,ksplit", [(200, 128, 1600, 3), (1000, 768, 2048, 4)])
+def test_exact_across_split_k_seams(cuda, M, N, K, ksplit, variant):
+    """vS split-K: (200, 128, 1600) splits its 25 K-tiles three ways, 8 / 8 / 9; (1000, 768, 2048) four ways.
+    NONE / BIAS / RESID must split — gemm_nt_ws_floats is ksplit·M·N > 0 — and round once (the splitk order); DMUL
+    and the other epilogues must not, and round in the staged order."""
+    k = _native.kernels()
+    ncu = _ncu()
+    seen = _probe(k, M, N, K, variant, ncu, want={"kernel": "vS"})
+    with gemm_mode(k, variant):
+        for epi in EPIS:
+            ws = k.gemm_nt_ws_floats(M, N, K, epi)
+            if epi in SPLITTABLE:
+                assert seen[epi]["ksplit"] == ksplit and ws == ksplit * M * N and ws > 0, (EPI_NAMES[epi], ws)
+            else:
+                assert seen[epi]["ksplit"] == 1 and ws == 0, (EPI_NAMES[epi], ws)
+    nk = K // 64
+    assert (M, N, K) != (200, 128, 1600) or [(s + 1) * nk // 3 - s * nk // 3 for s in range(3)] == [8, 8, 9]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("stagger", [HT, 0], ids=["tail", "notail"])
+@pytest.mark.parametrize("which,variant", [("n4096", 3), ("n4096", 0), ("n4096", 2), ("n2048", 2)])
+def test_exact_persistent_seam_half_tile_tail_grouped_order(cuda, which, variant, stagger):
+    """ncu + 16 tiles of 256²: the persistent v3 kernel runs a second tile on 16 workgroups (the tile seam) and,
+    with the tail on, that last wave as 128-row half tiles (forced v3; auto leaves so empty a last wave to vS, which
+    is asserted and probed all the same); forced v2 takes the grouped tile order gemm_nt2_kernel<EPI, 24> at
+    N / 256 = 16 (no tail there) and gemm_nt2_kernel<EPI, 8> with the tail at N = 2048."""
+    k = _native.kernels()
+    ncu = _ncu()
+    m16, m8, _ = persistent_shapes(ncu)
+    M, N, K = (m16, 4096, 128) if which == "n4096" else (m8, 2048, 128)
+    seen = _probe(k, M, N, K, variant, ncu, stagger=stagger)
+    d = seen[EPI_BIAS]
+    if variant == 0:
+        assert d["kernel"] == ("vS" if ncu == NCU_MI355X else d["kernel"])
+        return
+    rt = d["grid"] % ncu
+    assert d["grid"] > ncu and 0 < 2 * rt <= ncu, (d, ncu)                    # a second, at most half-full wave
+    if variant == 3:
+        assert all(s["kernel"] == "v3" for s in seen.values())
+        assert d["tail"] == bool(stagger) and not seen[EPI_DMUL]["tail"] and not seen[EPI_DGELU]["tail"]
+    elif which == "n4096":
+        assert all(s["kernel"] == "v2" and s["grouped"] and not s["tail"] for s in seen.values())
+    else:
+        assert all(s["kernel"] == "v2" and not s["grouped"] for s in seen.values())
+        assert d["tail"] == bool(stagger) and not seen[EPI_DMUL]["tail"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("sched", [1, 0], ids=["dynamic", "static"])
+def test_exact_dynamic_tile_scheduler(cuda, sched):
+    """2·ncu + 16 tiles on the persistent kernel: more than twice the workgroups, so with gemm_set_sched(1) a
+    workgroup's third tile comes from the ticket counters; the previous schedule is restored."""
+    k = _native.kernels()
+    ncu = _ncu()
+    before = k.gemm_get_sched()
+    M = persistent_shapes(ncu)[2]
+    seen = _probe(k, M, 4096, 128, 3, ncu, sched=sched)
+    assert all(s["kernel"] == "v3" and s["dynamic"] == bool(sched) and s["grid"] > 2 * ncu for s in seen.values())
+    assert k.gemm_get_sched() == before
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,kernel", [(0, "vS"), (1, "v1"), (2, "v2"), (3, "v3"), (4, "vS")])
+def test_exact_long_k(cuda, variant, kernel):
+    """K = 3072, which the bound tests leave out (gemm_oracle docstring): 48 K-tiles through each family's pipeline;
+    on vS the single tile row of four tiles splits four ways for NONE / BIAS / RESID."""
+    seen = _probe(_native.kernels(), 256, 256, 3072, variant, _ncu(), want={"kernel": kernel})
+    if kernel == "vS":
+        assert [seen[e]["ksplit"] for e in SPLITTABLE] == [4, 4, 4] and seen[EPI_BDR]["ksplit"] == 1
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M,N,K", [(100, 128, 64), (129, 128, 128), (1268, 256, 192), (1268, 256, 256)])
+def test_guards_past_m_and_past_the_part_rows(cuda, M, N, K):
+    """The M-tail shapes with N(0, 1)-like data: for every epilogue nothing past row M of C and P and nothing past
+    gemm_nt_part_rows of part changes (the canaries of ``_run``), and the last part row sums the rows below M only
+    (its bound)."""
+    k = _native.kernels()
+    inp = go.make_inputs(M, N, K, "small", device=cuda)
+    for variant in (0, 4):
+        with gemm_mode(k, variant):
+            for epi in EPIS:
+                kw = go.epi_args(inp, epi)
+                got = _run(k, inp["A"], inp["B"], epi, kw, K)
+                if epi in COL_PARTIALS:
+                    assert got["part"].shape[0] == -(-M // 128)
+                    o = go.oracle(inp["A"], inp["B"], epi, M_block=128, **kw)
+                    out = (got["part"].double() - o["part"]).abs() > go.bounds(o)["part"]
+                    assert not bool(out.any()), (EPI_NAMES[epi], out.nonzero()[:4].tolist())
+
+
+# ------------------------------------------------------------------------------------------- TN weight gradient
+@pytest.mark.gpu
+@pytest.mark.parametrize("T,N,K", [(128, 256, 256), (200, 256, 512), (1268, 768, 256), (4159, 256, 256)])
+def test_gemm_tn_exact(cuda, T, N, K):
+    """dW = dyᵀ·x and the fused bias gradient with integer dy, x in [−3, 3] (every partial sum an integer below
+    2²⁴ in any order and split): bitwise against the float64 product for the split counts auto, 1 and 3 where
+    allowed, plain and accumulating onto an integer base, with and without bias_out, TN variants 0, 1 and 5; token
+    tails T % 64 != 0 included."""
+    k = _native.kernels()
+    dy = (go._hash(T * N, 11, cuda) % 7 - 3).view(T, N).bfloat16()
+    x = (go._hash(T * K, 12, cuda) % 7 - 3).view(T, K).bfloat16()
+    base = (go._hash(N * K, 13, cuda) % 2001 - 1000).view(N, K).float()
+    b0 = (go._hash(N, 14, cuda) % 2001 - 1000).float()
+    ref = (dy.double().t() @ x.double())
+    db = dy.double().sum(0)
+    assert float(ref.abs().max()) + 1000 < 2 ** 24 and bool((ref != 0).any())
+    ref, db = ref.float(), db.float()
+    assert k.gemm_tn_splits(T, N, K) >= 1
+    splits = [0] + [s for s in (1, 3) if (T + 63) // 64 // s >= 2]
+    assert 1 in splits and (3 in splits) == (T >= 384)
+    try:
+        for v in (0, 1, 5):
+            k.gemm_tn_set_variant(v)
+            for s in splits:
+                what = (v, s)
+                out = torch.full((N, K), CANARY, device=cuda)
+                k.gemm_tn(dy, x, out, False, s)
+                assert torch.equal(out, ref), what
+                out = base.clone()
+                k.gemm_tn(dy, x, out, True, s)
+                assert torch.equal(out, base + ref), what
+                out, dbo = torch.full((N, K), CANARY, device=cuda), torch.full((N,), CANARY, device=cuda)
+                k.gemm_tn(dy, x, out, False, s, dbo)
+                assert torch.equal(out, ref) and torch.equal(dbo, db), what
+                out, dbo = base.clone(), b0.clone()
+                k.gemm_tn(dy, x, out, True, s, dbo)
+                assert torch.equal(out, base + ref) and torch.equal(dbo, b0 + db), what
+    finally:
+        k.gemm_tn_set_variant(0)
