@@ -592,8 +592,9 @@ std::vector<Tensor> attn_fwd(Tensor qkv, Tensor key_bias, int64_t B, int64_t L, 
 // write_bf16 = false: [empty, dqkv8, bpart] — no bf16 dQKV, the QKV bias-gradient column partials
 // bpart [B·ceil(L/32), 3H] instead (colsum_into reduces them)
 std::vector<Tensor> attn_bwd_impl(Tensor dctx, Tensor qkv, Tensor ctx, Tensor lse, Tensor key_bias, Tensor mbits, int64_t B,
-                                  int64_t L, int64_t nh, double p, double scale, bool deterministic,
+                                  int64_t L, int64_t nh, double p, double scale, bool /*deterministic*/,
                                   c10::optional<Tensor> q8, int64_t phase, bool write_bf16 = true) {
+  // `deterministic` is accepted and ignored: both backward kernels are deterministic (no atomics)
   check_attn(qkv, key_bias, B, L, nh);
   check(dctx, BF16, "dctx"); check(ctx, BF16, "ctx"); check(lse, F32, "lse");
   const int64_t H = qkv.size(1) / 3;
@@ -613,7 +614,7 @@ std::vector<Tensor> attn_bwd_impl(Tensor dctx, Tensor qkv, Tensor ctx, Tensor ls
   Tensor dqkv8 = want8 ? at::empty(qkv.sizes(), qkv.options().dtype(at::kFloat8_e5m2)) : Tensor();
   hq_attn_bwd(ptr<uint16_t>(dctx), ptr<uint16_t>(qkv), ptr<uint16_t>(ctx), ptr<float>(lse), ptr<float>(key_bias),
               p > 0 ? ptr<uint16_t>(mbits) : nullptr, write_bf16 ? ptr<uint16_t>(dqkv) : nullptr, ptr<float>(delta), (int)B,
-              (int)L, (int)nh, 64, (float)p, (float)scale, deterministic, cur_stream(),
+              (int)L, (int)nh, 64, (float)p, (float)scale, cur_stream(),
               want8 ? reinterpret_cast<uint8_t*>(dqkv8.data_ptr()) : nullptr, q8p, (int)(phase % 3),
               write_bf16 ? nullptr : ptr<float>(bpart));
   if (!write_bf16) return {dqkv, dqkv8, bpart};

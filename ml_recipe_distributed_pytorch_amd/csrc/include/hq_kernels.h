@@ -136,7 +136,7 @@ void hq_f32_attn_bwd(const float* dctx, const float* qkv, const float* ctx, cons
                      float* dqkv, float* delta, int B, int L, int nh, float p, uint32_t seed, uint32_t opid, float scale,
                      hipStream_t s);
 
-// ---- attention.hip ----------------------------------------------------------------------------
+// ---- attention_fwd.hip, attention_bwd.hip (shared device code: hq_attn.h) -----------------------
 void hq_attn_set_force_slow(int v);          // tests: every ring-forward workgroup takes the slow path
 size_t hq_attn_mask_bytes(int B, int L, int nh);   // dropout keep-bits written by fwd, read by bwd
 // ctx8 / q8 / phase (optional, --precision fp8): ctx also written as e4m3 under the delayed-scaling state q8;
@@ -146,7 +146,7 @@ void hq_attn_fwd(const uint16_t* qkv, const float* key_bias, uint16_t* ctx, floa
                  uint8_t* ctx8 = nullptr, float* q8 = nullptr, int phase = 0);
 void hq_attn_bwd(const uint16_t* dctx, const uint16_t* qkv, const uint16_t* ctx, const float* lse, const float* key_bias,
                  const uint16_t* mbits, uint16_t* dqkv, float* delta, int B, int L, int nh, int dh, float p, float scale,
-                 bool deterministic, hipStream_t s, uint8_t* dqkv8 = nullptr, float* q8 = nullptr, int phase = 0,
+                 hipStream_t s, uint8_t* dqkv8 = nullptr, float* q8 = nullptr, int phase = 0,
                  float* bpart = nullptr);
 // bpart != null (with dqkv8): dqkv (bf16) is NOT written; instead the QKV bias-gradient column partials
 // bpart[B·ceil(L/32)][3H] (sum over rows = Σ_t dQKV[t, :]) for the fp8 weight gradient.

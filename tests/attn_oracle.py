@@ -6,9 +6,9 @@ Everything here runs on the CPU and takes nothing from a kernel.  Heads are [B, 
 ``oracle``   exact (float64) softmax attention forward and backward of the bf16 or fp32 inputs with its own lse, ctx
              and δ, the dropout mask of ``ops.rng.keep_mask``, and beside each output the sum of the absolute values
              of the terms that were added to form it (the running-error scale A of the per-row bound).
-``emulate``  the same computation in fp32 with the bf16 roundings that csrc/kernels/attention.hip performs.  It is
-             the noise model the bounds of the tests are derived from; it models neither the kernels' accumulation
-             order, nor FMA contraction, nor the hardware's exp2 / log2.
+``emulate``  the same computation in fp32 with the bf16 roundings that csrc/kernels/attention_fwd.hip and
+             attention_bwd.hip perform.  It is the noise model the bounds of the tests are derived from; it models
+             neither the kernels' accumulation order, nor FMA contraction, nor the hardware's exp2 / log2.
 ``MUTANTS``  mistakes planted in the oracle's backward; each must be rejected by the bounds.
 """
 import functools
@@ -156,8 +156,9 @@ def _exp2(x):
 
 
 def emulate(qkv, kb, dctx, B, L, nh, p, keep, scale=SCALE):
-    """The bf16 kernels' arithmetic (attention.hip) in fp32 tensors — every elementwise result rounded to fp32 as in
-    the VALU code, every matmul once as an MFMA accumulator (``_mm``) — with the kernels' bf16 roundings:
+    """The bf16 kernels' arithmetic (attention_fwd.hip, attention_bwd.hip) in fp32 tensors — every elementwise
+    result rounded to fp32 as in the VALU code, every matmul once as an MFMA accumulator (``_mm``) — with the
+    kernels' bf16 roundings:
 
     * Q·c rounded to bf16 with c = scale·log2e in fp32 (``prescale8``; hq_attn_fwd / hq_attn_bwd pass
       ``scale * LOG2E`` as a float: c itself is not rounded to bf16);

@@ -1,5 +1,5 @@
-"""Attention kernels (csrc/kernels/attention.hip, the fp32 flash attention of f32_attention.hip) against a float64 oracle
-with per-row error bounds, and exact probes of every (query, key) term.
+"""Attention kernels (csrc/kernels/attention_fwd.hip, attention_bwd.hip, the fp32 flash attention of
+f32_attention.hip) against a float64 oracle with per-row error bounds, and exact probes of every (query, key) term.
 
 Oracle (tests/attn_oracle.py): float64 forward and backward from the bf16 inputs; its own lse, ctx and δ; the
 dropout mask of ``ops.rng.keep_mask``.  Beside each output it returns the sum of the absolute values of the terms
@@ -354,11 +354,12 @@ def _close_codes(got, exp, frac):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("L", [100, 160])
+@pytest.mark.parametrize("L", [100, 160, 128, 256, 512])
 @pytest.mark.parametrize("p", [0.0, 0.1])
 def test_fp8_backward_modes_away_from_384(cuda, L, p):
     """The e5m2-writing backward (MODE 1) and the e5m2-only backward with bias-gradient partials (MODE 2): a ring
-    three tiles deep and another LDS layout than the bf16 path, in the rolled ragged and rolled even kernels."""
+    three tiles deep and another LDS layout than the bf16 path, in the rolled ragged and rolled even kernels and the
+    unrolled ones of L = 128, 256, 512 (384: tests/test_fp8_gpu.py)."""
     from test_fp8_gpu import _q5
     case = (3, L, 3, p, "tail", 0.0)
     B, nh, H = 3, 3, 192
@@ -388,7 +389,7 @@ def test_fp8_backward_modes_away_from_384(cuda, L, p):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("L", [100, 160])
+@pytest.mark.parametrize("L", [100, 160, 128, 256, 512])
 @pytest.mark.parametrize("p", [0.0, 0.1])
 def test_fp8_forward_ctx8_away_from_384(cuda, L, p):
     """The forward with the e4m3 copy of ctx: ctx, lse and the keep bits are the plain forward's bitwise, and

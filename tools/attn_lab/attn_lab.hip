@@ -1,6 +1,6 @@
 // Attention-forward lab: times the production forward against instrumented / restructured variants
 // at one BERT shape (hipEvent timing, no torch).  Build + run: tools/attn_lab/run.sh
-#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/attention.hip"
+#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/attention_fwd.hip"
 
 #include <cmath>
 #include <cstring>
@@ -11,7 +11,7 @@ namespace {
 
 typedef float f2_t __attribute__((ext_vector_type(2)));
 
-// single-matrix prologue loader (the production kernels now use load_heads2 for K and V together)
+// single-matrix prologue loader of the whole-head variants below
 template <int NT>
 __device__ __forceinline__ void load_head(uint16_t* dst, const uint16_t* src, size_t ld, int L, int Lp) {
   for (int t = threadIdx.x; t < Lp * 8; t += NT) {

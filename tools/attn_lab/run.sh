@@ -1,8 +1,11 @@
 #!/usr/bin/env bash
 # Build and run the attention lab on the GPU box: bash tools/attn_lab/run.sh [B]
+# (fp8.hip and rowops.hip hold the amax-partial and dropout-key helpers that hq_attn_fwd calls)
 set -eo pipefail
 cd "$(dirname "$0")/../.."
 mkdir -p gpurun_out/attn_lab
+K=ml_recipe_distributed_pytorch_amd/csrc/kernels
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -Iml_recipe_distributed_pytorch_amd/csrc/include \
+  $K/fp8.hip $K/rowops.hip \
   tools/attn_lab/attn_lab.hip -o gpurun_out/attn_lab/attn_lab
 timeout -k 10 120 gpurun_out/attn_lab/attn_lab "${1:-256}" | tee gpurun_out/attn_lab/out.txt

@@ -12,7 +12,8 @@ folds from gemm_fp8.hip to fp8.hip, name every file the subject moved between (a
 link has duplicate or missing hq_* symbols; a subject whose file does not exist at REV (embed / sort / rowops.hip)
 cannot be overlaid from before that commit — build that revision whole in a worktree instead.  Likewise across the
 commit that split the fp32 ops file into f32_embed / f32_norm / f32_rowops / f32_attention.hip: from before it, build the whole revision in a worktree
-(AB_DIR still picks where the library goes).
+(AB_DIR still picks where the library goes).  And across the commit that split attention.hip into attention_fwd.hip,
+attention_bwd.hip and include/hq_attn.h: from before it, build the parent whole in a worktree.
 """
 import os
 import shutil

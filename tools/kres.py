@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel register / scratch / occupancy table from hipcc's kernel-resource-usage remarks.
 
-    python tools/kres.py csrc/kernels/attention.hip [--match ring]
+    python tools/kres.py csrc/kernels/attention_bwd.hip [--match ring]
 """
 import argparse
 import re
