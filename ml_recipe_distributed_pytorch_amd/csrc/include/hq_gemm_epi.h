@@ -1,4 +1,4 @@
-// The epilogue of the NT GEMMs, once: every kernel of gemm.hip (v1, vS, v2, v3) turns a staged piece into its C
+// The epilogue of the NT GEMMs, once: every kernel of gemm_nt_v1 / _vs / _v2 / _v3.hip turns a staged piece into its C
 // piece, P piece and column sums with hq_epi_piece below, so "every variant computes the same C and P" is a
 // property of the code.  Device code only; what differs per kernel stays with the kernel: where the staged piece
 // and the operand piece come from, and how the stores are issued (v3: buffer stores with a cache policy and held

@@ -208,7 +208,7 @@ void hq_lamb_apply(float* master, uint16_t* compute, const float* m, const float
 void hq_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, float scale, hipStream_t s);
 void hq_cast_bf16_f32(const uint16_t* src, float* dst, int64_t n, float scale, hipStream_t s);
 
-// ------------------------------------------------------------------ MFMA GEMM (gemm.hip)
+// ------------------------------------------------------------------ MFMA GEMM (gemm_nt.hip; kernels: gemm_nt_v*.hip)
 enum { HQ_EPI_NONE = 0, HQ_EPI_BIAS = 1, HQ_EPI_GELU = 2, HQ_EPI_DGELU = 3, HQ_EPI_RESID = 4, HQ_EPI_GELUD = 5, HQ_EPI_DMUL = 6,
        HQ_EPI_BDR = 7 };
 // what an epilogue touches beside C (host and device): the fp32 bias; a second bf16 [M,N] operand (DGELU / DMUL: P,

@@ -1,7 +1,7 @@
 // OCP fp8 (e4m3fn) "NT" GEMM for the --precision fp8 forward projections on gfx950:
 //   C[M,N] = (A8[M,K] · B8[N,K]ᵀ) · sa · sb (+ epilogue),  A8/B8 e4m3, sa/sb per-tensor dequant scales.
 //
-// The pipeline is gemm.hip's v2 (256×256 output tile, 8 ping-ponging waves, four phases per K-tile,
+// The pipeline is gemm_nt_v2.hip's (256×256 output tile, 8 ping-ponging waves, four phases per K-tile,
 // one 16 KiB half-panel of buffer_load…lds per phase under a counted vmcnt(6)) with the byte-identical
 // LDS image: a K-tile is 128 fp8 = 128 B per row, exactly the bf16 kernel's 64 × 2 B rows.  What
 // changes is the matrix core: v_mfma_scale_f32_16x16x128_f8f6f4 (block-scaled MX form, unit e8m0
@@ -27,14 +27,19 @@
 
 #include "hq_common.h"
 #include "hq_gemm_epi.h"
+#include "hq_gemm_tile.h"
 #include "hq_kernels.h"
 
 namespace {
 
-constexpr int BM = 256, BN = 256, BK = 128;  // BK in fp8 elements (= bytes)
-constexpr int kThreads = 512;
+using hq_tile::bar;
+using hq_tile::kRawBufferWord3;
+using hq_tile::kThreads;
+using hq_tile::lds_void;
+using hq_tile::stage_half;
 
-typedef __attribute__((address_space(3))) void lds_void;
+constexpr int BM = 256, BN = 256, BK = 128;  // BK in fp8 elements (= bytes)
+
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 
 // w: the weight fragment (always e4m3, format code 0); x: the activation fragment, e4m3 (0) in the
@@ -158,8 +163,8 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_kernel(const uint8_t* __
   const int nt = K / BK;
   if constexpr (Q8) hq_fp8_publish_scale(q8, phase, EPI == HQ_EPI_DMUL ? kHqBf8Max : kHqFp8Max);
 
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, (short)0, BM * lda, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, (short)0, BN * ldb, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, (short)0, BM * lda, kRawBufferWord3);
+  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, (short)0, BN * ldb, kRawBufferWord3);
   int voA[2], voB[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -168,6 +173,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_kernel(const uint8_t* __
     voA[i] = row * lda + src_slot * 16;
     voB[i] = row * ldb + src_slot * 16;
   }
+  // (hq_tile::stage_half's text; through the function this kernel's scalar code around the loads changes)
   auto half = [&](const __amdgpu_buffer_rsrc_t& rs, const int (&vo)[2], int ld, int h, int t, char* panel) {
     char* dst = panel + (h * 128 + wave_u * 16) * 128;
     const int so = h * 128 * ld + t * BK;
@@ -206,16 +212,11 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_kernel(const uint8_t* __
       for (int j = 0; j < 2; ++j) acc[mh * 4 + i][nh * 2 + j] = mfma_fp8<FX>(bf[j], af[i], acc[mh * 4 + i][nh * 2 + j]);
     __builtin_amdgcn_s_setprio(0);
   };
-  auto bar = []() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
 
   stA(0, 0); stB(0, 0); stB(1, 0); stA(1, 0); stA(0, 1); stB(0, 1); stB(1, 1);
   asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   bar();
-  // two 32-MFMA phases per K-tile; stage / wait table and hazard argument: gemm.hip, gemm_nt3_kernel
+  // two 32-MFMA phases per K-tile; stage / wait table and hazard argument: hq_gemm_tile.h
   auto ktile = [&](int t) {
     const bool more1 = t + 1 < nt, more2 = t + 2 < nt;
     if (t == 0 || more1) asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -227,7 +228,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_kernel(const uint8_t* __
     mma(0, 0, bf0);
     mma(0, 1, bf1);
     bar();
-    // both wave rows (gemm.hip, gemm_nt3_kernel P23)
+    // both wave rows (hq_gemm_tile.h, the P23 wait)
     if (more1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     readA(t, 1);
     if (more2) { stA(0, t + 2); stB(0, t + 2); stB(1, t + 2); }
@@ -244,7 +245,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_kernel(const uint8_t* __
     for (int t = 0; t < nt; ++t) ktile(t);
   }
 
-  // ---- epilogue: acc · (sa·sb) (+bias) -> bf16 staging (as gemm.hip v2), then row-coalesced pieces
+  // ---- epilogue: acc · (sa·sb) (+bias) -> bf16 staging (as gemm_nt_v2.hip), then row-coalesced pieces
   const float dq = sa[0] * sb[0];
   constexpr int WN = 64, RS = WN * 2 + 16;
   constexpr bool kBias = EPI == HQ_EPI_BIAS || EPI == HQ_EPI_GELUD;
@@ -269,13 +270,13 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_kernel(const uint8_t* __
   }
   constexpr int SEGS = WN / 8, ROWS_PER_IT = 64 / SEGS, NIT = 128 / ROWS_PER_IT;
   const int seg = lane % SEGS, rsub = lane / SEGS;
-  const int gcol = n0 + wn * 64 + seg * 8;   // full 128-B lines per store (gemm.hip gemm_nt3_kernel)
+  const int gcol = n0 + wn * 64 + seg * 8;   // full 128-B lines per store (gemm_nt_v3.hip)
   auto grow_of = [&](int it) {
     const int lr = it * ROWS_PER_IT + rsub;
     return m0 + (lr >> 6) * 128 + wm * 64 + (lr & 63);
   };
   // DMUL's gelu' / RESID's residual (both via P): all 16 pieces of this lane issued at once (one exposed
-  // HBM latency, gemm.hip v2)
+  // HBM latency, gemm_nt_v2.hip)
   constexpr bool kAux = EPI == HQ_EPI_DMUL || EPI == HQ_EPI_RESID;
   uint4 aux[kAux ? NIT : 1];
   float csum[8];
@@ -316,11 +317,11 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8_kernel(const uint8_t* __
   }
 }
 
-// ------------------------------------------------------------------ persistent form (gemm.hip v3)
+// ------------------------------------------------------------------ persistent form (gemm_nt_v3.hip)
 // At K = 768 a 256² fp8 tile is only 6 K-tiles, so v2's per-tile fixed cost (workgroup launch, the
 // prologue's first HBM round trip, the epilogue's drain) is about half of it.  This form keeps ONE workgroup
 // per CU walking tiles (tile = id, id + grid, …) and runs the LDS-DMA pipeline across the tile seam exactly
-// as gemm.hip's gemm_nt3_kernel (same LDS plan, phase table and counted waits — the fp8 K-tile has the bf16
+// as gemm_nt_v3.hip's gemm_nt3_kernel (same LDS plan, phase table and counted waits — the fp8 K-tile has the bf16
 // one's byte geometry): the next tile's K-tile 0 is staged during this tile's last two K-tiles, its K-tile-1
 // first halves after the epilogue, which borrows the last K-tile's buffer (two 64-row rounds per wave).
 // The epilogue's vm ops per lane (E) are counted into the next tile's first waits.  Amax partials: one per
@@ -367,22 +368,16 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8p_kernel(const uint8_t* _
     voB[i] = row * ldb + src_slot * 16;
   }
   auto rsrc_a = [&](int tile) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(A + (size_t)(tile / tiles_n) * BM * lda), (short)0, BM * lda, 0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(A + (size_t)(tile / tiles_n) * BM * lda), (short)0, BM * lda, kRawBufferWord3);
   };
   auto rsrc_b = [&](int tile) {
-    return __builtin_amdgcn_make_buffer_rsrc((void*)(B + (size_t)(tile % tiles_n) * BN * ldb), (short)0, BN * ldb, 0x00020000);
+    return __builtin_amdgcn_make_buffer_rsrc((void*)(B + (size_t)(tile % tiles_n) * BN * ldb), (short)0, BN * ldb, kRawBufferWord3);
   };
   auto stA = [&](__amdgpu_buffer_rsrc_t rs, int half, int kt, int buf) {
-    char* dst = smem + buf * STAGE + (half * 128 + wave_u * 16) * 128;
-    const int so = half * 128 * lda + kt * BK;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(dst + i * 8 * 128), 16, voA[i], so, 0, 0);
+    stage_half<1>(rs, voA, lda, half, kt, smem + buf * STAGE, wave_u);
   };
   auto stB = [&](__amdgpu_buffer_rsrc_t rs, int half, int kt, int buf) {
-    char* dst = smem + buf * STAGE + PANEL + (half * 128 + wave_u * 16) * 128;
-    const int so = half * 128 * ldb + kt * BK;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void*)(dst + i * 8 * 128), 16, voB[i], so, 0, 0);
+    stage_half<1>(rs, voB, ldb, half, kt, smem + buf * STAGE + PANEL, wave_u);
   };
 
   f32x4_t acc[8][4];
@@ -408,11 +403,6 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8p_kernel(const uint8_t* _
 #pragma unroll
       for (int j = 0; j < 2; ++j) acc[mh * 4 + i][nh * 2 + j] = mfma_fp8<FX>(bf[j], af[i], acc[mh * 4 + i][nh * 2 + j]);
     __builtin_amdgcn_s_setprio(0);
-  };
-  auto bar = []() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
   };
 
   const float dq = sa[0] * sb[0];
@@ -442,7 +432,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8p_kernel(const uint8_t* _
     for (int i = 0; i < 8; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    // two 32-MFMA phases per K-tile; stage / wait table and hazard argument: gemm.hip gemm_nt3_kernel
+    // two 32-MFMA phases per K-tile; stage / wait table and hazard argument: hq_gemm_tile.h
     auto ktile = [&](int t) {
       const bool more1 = t + 1 < nt || !last;
       const bool more2 = t + 2 < nt || (t + 2 == nt && !last);
@@ -467,7 +457,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8p_kernel(const uint8_t* _
       mma(0, 0, bf0);
       mma(0, 1, bf1);
       bar();
-      // both wave rows (gemm.hip, gemm_nt3_kernel P23); at t = 0 of a following unit the epilogue's E vm ops
+      // both wave rows (hq_gemm_tile.h, the P23 wait); at t = 0 of a following unit the epilogue's E vm ops
       // are younger too
       if (t == 0 && !first) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 + E) : "memory");
       else if (more1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
@@ -493,7 +483,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_fp8p_kernel(const uint8_t* _
     constexpr int SEGS = WN / 8, ROWS_PER_IT = 64 / SEGS;
     constexpr bool kBias = EPI == HQ_EPI_BIAS || EPI == HQ_EPI_GELUD;
     const int seg = lane % SEGS, rsub = lane / SEGS;
-    const int gcol = n0 + wn * 64 + seg * 8;   // full 128-B lines per store (gemm.hip gemm_nt3_kernel)
+    const int gcol = n0 + wn * 64 + seg * 8;   // full 128-B lines per store (gemm_nt_v3.hip)
     float csum[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) csum[e] = 0.f;

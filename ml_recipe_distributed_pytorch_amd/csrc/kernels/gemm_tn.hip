@@ -3,7 +3,7 @@
 // split-K over the T tokens into S fp32 partial slabs, then hq_splitk_reduce adds the slabs into the
 // fp32 grad arena (optionally accumulating).  Replaces hipBLASLt's batched split-K wgrad.
 //
-// Same pipeline as gemm.hip's v2 NT kernel (256×256 output tile, 64-token K-tiles, 8 waves as
+// Same pipeline as gemm_nt_v2.hip's NT kernel (256×256 output tile, 64-token K-tiles, 8 waves as
 // 2 (N) × 4 (K) ping-ponging wave groups, four phases per K-tile, one 16 KiB half-panel of LDS-DMA
 // per phase with three halves in flight under a counted vmcnt(6), buffer_load … lds with the K-tile
 // advance in the scalar offset).  What differs is the operand layout: a half-panel is a
@@ -33,21 +33,21 @@
 #include <cstdlib>
 
 #include "hq_common.h"
+#include "hq_gemm_tile.h"
 #include "hq_kernels.h"
 
 namespace {
 
+using hq_tile::bar;
+using hq_tile::kRawBufferWord3;
+using hq_tile::kThreads;
+using hq_tile::lds_void;
+using hq_tile::mfma16;
+
 constexpr int BT = 64;          // tokens per K-tile
-constexpr int kThreads = 512;
 constexpr int HALF = BT * 256;  // [64 tokens][128 bf16] = 16 KiB
 constexpr int STAGE = 4 * HALF; // A0 A1 B0 B1
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(3))) bf16x4_t lds_bf16x4;
-
-__device__ __forceinline__ f32x4_t mfma16(const bf16x8_t& a, const bf16x8_t& b, const f32x4_t& c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
 __device__ __forceinline__ int tswz(int t) { return (t & 3) | (((t >> 3) & 1) << 2); }
 // f(integral_constant<int, n>) for n = 0 … N-1, fully unrolled in order
 template <typename F, int... n>
@@ -97,8 +97,8 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const uint16_t* __
 
   const uint16_t* Ab = A + (size_t)kt0 * BT * N + n0;
   const uint16_t* Bb = B + (size_t)kt0 * BT * K + k0;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, (short)0, rows * N * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, (short)0, rows * K * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, (short)0, rows * N * 2, kRawBufferWord3);
+  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, (short)0, rows * K * 2, kRawBufferWord3);
 
   // staging: wave w moves rows (2w + i)·4 … +3 of a half (1 KiB per instruction, lane-linear:
   // lane L → row +L/16, 16-B slot L%16), loading the source chunk that the swizzle places there
@@ -176,11 +176,6 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const uint16_t* __
     }
     __builtin_amdgcn_s_setprio(0);
   };
-  auto bar = []() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
 
   // prologue (always real loads): tile 0 A0 B0 B1 A1, tile 1 A0 B0 B1; retire tile 0
   {
@@ -201,7 +196,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const uint16_t* __
   asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
   bar();
 
-  // two phases of 32 MFMAs per K-tile (schedule, waits and hazard argument: gemm.hip, gemm_nt3_kernel):
+  // two phases of 32 MFMAs per K-tile (schedule, waits and hazard argument: hq_gemm_tile.h):
   //   P01: reads B(0) A(0) B(1), stages A1 of t+1 | (0,0) (0,1);   P23: reads A(1), stages A0 B0 B1 of t+2 | (1,1) (1,0)
   auto ktile = [&](int t) {
     const bool more1 = t + 1 < nt, more2 = t + 2 < nt;
@@ -216,7 +211,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn_kernel(const uint16_t* __
     mma(0, 1, bf1);
     bar();
     // A0 B0 B1 of t+1 (read by both wave rows in their next P01): younger is this P01's A1 stage.  Both rows
-    // wait (gemm.hip, gemm_nt3_kernel P23: each half's rows come from all 8 waves)
+    // wait (hq_gemm_tile.h, the P23 wait: each half's rows come from all 8 waves)
     if (more1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     readA(t, 1);
     if (more2) { stA(0, t + 2); stB(0, t + 2); stB(1, t + 2); }
@@ -289,8 +284,8 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn2_kernel(const uint16_t* _
 
   const uint16_t* Ab = A + (size_t)kt0 * BT * N + n0;
   const uint16_t* Bb = B + (size_t)kt0 * BT * K + k0;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, (short)0, rows * N * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, (short)0, rows * K * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, (short)0, rows * N * 2, kRawBufferWord3);
+  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, (short)0, rows * K * 2, kRawBufferWord3);
   int voA[2], voB[2];
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
@@ -350,11 +345,6 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn2_kernel(const uint16_t* _
   };
   using I0 = std::integral_constant<int, 0>;
   using I1 = std::integral_constant<int, 1>;
-  auto bar = []() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
   // one of the 8 DMA instructions of K-tile t: A half 0/1, B half 0/1, two 1-KiB rows blocks each
   auto stage_one = [&](auto pc_c, int t) {
     constexpr int PC = decltype(pc_c)::value, W = PC >> 1, I = PC & 1;
@@ -486,8 +476,8 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn8_kernel(const uint8_t* __
 
   const uint8_t* Ab = A + (size_t)kt0 * BT8 * N + n0;
   const uint8_t* Bb = B + (size_t)kt0 * BT8 * K + k0;
-  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, (short)0, rows * N, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, (short)0, rows * K, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc((void*)Ab, (short)0, rows * N, kRawBufferWord3);
+  const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc((void*)Bb, (short)0, rows * K, kRawBufferWord3);
 
   // staging: wave w moves rows (2w + i)·8 … +7 of a half (1 KiB per instruction, lane-linear: lane L → row
   // +L/8, 16-B slot L%8), loading the source chunk that the swizzle places there
@@ -538,11 +528,6 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn8_kernel(const uint8_t* __
       for (int j = 0; j < 2; ++j) acc[mh * 4 + i][nh * 2 + j] = mfma_tn8(bf[j], af[i], acc[mh * 4 + i][nh * 2 + j]);
     __builtin_amdgcn_s_setprio(0);
   };
-  auto bar = []() {
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
 
   // prologue, schedule and waits: identical to gemm_tn_kernel (2 DMA instructions per wave per half)
   stA(0, 0); stB(0, 0); stB(1, 0); stA(1, 0); stA(0, 1); stB(0, 1); stB(1, 1);
@@ -559,7 +544,7 @@ __global__ __launch_bounds__(kThreads, 1) void gemm_tn8_kernel(const uint8_t* __
     mma(0, 0, bf0);
     mma(0, 1, bf1);
     bar();
-    // both wave rows (gemm.hip, gemm_nt3_kernel P23)
+    // both wave rows (hq_gemm_tile.h, the P23 wait)
     if (more1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     readA(t, 1);
     if (more2) { stA(0, t + 2); stB(0, t + 2); stB(1, t + 2); }

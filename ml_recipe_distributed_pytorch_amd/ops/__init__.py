@@ -1,7 +1,7 @@
 """Fused-op API used by the model.  Dispatch is by device, not by a backend registry:
 
 * CUDA (ROCm/HIP) tensors → hand-written gfx950 kernels in ``_hq_kernels.so`` (fail loudly if absent):
-  embedding, LayerNorm, attention, optimizer, heads, and the MFMA GEMMs (``gemm.hip`` NT with fused
+  embedding, LayerNorm, attention, optimizer, heads, and the MFMA GEMMs (``gemm_nt*.hip`` NT with fused
   epilogues for every encoder projection forward and dgrad, ``gemm_tn.hip`` split-K weight gradients).
   No vendor BLAS: an untileable shape raises.
 * CPU tensors → ``ops.reference`` (pure PyTorch, fp32), which is also the numerics oracle.
@@ -183,7 +183,7 @@ def attn_bwd(dctx, qkv, ctx, lse, key_bias, bits, B, L, nh, p, seed, opid, scale
 
 
 # --------------------------------------------------------------------------------------- linear
-# Every projection GEMM on the GPU runs on the hand-written gfx950 MFMA kernels: ``gemm.hip`` (NT, C = A·Bᵀ
+# Every projection GEMM on the GPU runs on the hand-written gfx950 MFMA kernels: ``gemm_nt*.hip`` (NT, C = A·Bᵀ
 # with fused epilogues, every forward projection and dgrad) and ``gemm_tn.hip`` (split-K weight gradients).
 # There is no vendor-BLAS fallback: a shape the kernels do not tile raises instead of silently running
 # something else (BERT / RoBERTa base and large, and the tiny test config, all tile).
@@ -200,7 +200,7 @@ LN_FROM_Y = os.environ.get("HQ_LN_FROM_Y", "1") == "1"
 
 
 def _check_nt(M: int, N: int, K: int, what: str):
-    """Raise unless C[M, N] = A[M, K]·B[N, K]ᵀ tiles on gemm.hip (N % 128 == 0, K % 64 == 0; any M)."""
+    """Raise unless C[M, N] = A[M, K]·B[N, K]ᵀ tiles on the NT GEMM kernels (gemm_nt.hip) (N % 128 == 0, K % 64 == 0; any M)."""
     if _k().gemm_nt_supported(int(M), int(N), int(K)) <= 0:
         raise RuntimeError(f"{what}: GEMM M={M} N={N} K={K} does not tile on the gfx950 MFMA kernels "
                            "(needs N % 128 == 0 and K % 64 == 0)")

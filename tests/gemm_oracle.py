@@ -3,7 +3,7 @@ GEMM tests (test_gemm_oracle_gpu.py).  Nothing here takes a value from a kernel;
 of its inputs, so the CPU tests and the GPU tests share the code.
 
 ``oracle``     C = A·Bᵀ of the bf16 inputs in float64 with S = |A|·|B|ᵀ (the sum of the absolute terms), the exact
-               result of each of the eight epilogues of csrc/kernels/gemm.hip (C, P where the epilogue writes it,
+               result of each of the eight epilogues of csrc/include/hq_gemm_epi.h (C, P where the epilogue writes it,
                the column sums per ``M_block`` rows for DGELU / DMUL), GELU in the erf form (``torch.erfc``), the
                BDR keep mask from ``ops.rng.keep_mask`` at the element index m·N + n.
 ``bounds``     per element, from the oracle's float64 values alone, how far a correct kernel may be from them.

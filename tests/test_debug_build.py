@@ -21,7 +21,8 @@ HIPCC = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "bin", "hipcc")
 def test_debug_kernels_compile(tmp_path):
     # the row-wise kernel files: LayerNorm, the embedding (id and partial-row assertions), its sort, the column sums;
     # and the NT GEMMs (tile-bound assertions), whose kernels share the epilogue of include/hq_gemm_epi.h
-    for name in ("norm", "embed", "sort", "rowops", "gemm", "gemm_fp8"):
+    for name in ("norm", "embed", "sort", "rowops", "gemm_nt", "gemm_nt_v1", "gemm_nt_vs", "gemm_nt_v2", "gemm_nt_v3",
+                 "gemm_fp8"):
         src = os.path.join(CSRC, "kernels", name + ".hip")
         out = tmp_path / (name + "_debug.o")
         r = subprocess.run([HIPCC, "-O3", "-fPIC", "-std=c++17", "--offload-arch=gfx950", "-DHQ_DEBUG=1",

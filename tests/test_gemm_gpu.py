@@ -1,4 +1,4 @@
-"""MFMA NT GEMM (gemm.hip) vs an fp32 torch reference, every epilogue, every kernel variant:
+"""MFMA NT GEMM (gemm_nt*.hip) vs an fp32 torch reference, every epilogue, every kernel variant:
 auto (0: 128² tiles for M tails / low CU fill, else the persistent v3 for K <= 2304 and v2 above),
 v1 (whole-tile staging), forced v2 (deep LDS-DMA pipeline, also at K <= 2304), forced v3 (persistent,
 also at K = 3072) and forced vS (the 128²-tile kernel everywhere)."""

@@ -1,4 +1,4 @@
-"""bf16 NT GEMM (csrc/kernels/gemm.hip, the shared epilogue of csrc/include/hq_gemm_epi.h) and the TN weight gradient
+"""bf16 NT GEMM (csrc/kernels/gemm_nt*.hip, the shared epilogue of csrc/include/hq_gemm_epi.h) and the TN weight gradient
 (gemm_tn.hip) against a float64 oracle with per-element bounds, and exact integer probes of every dispatch path.
 
 tests/gemm_oracle.py holds the oracle, the bounds, the fp32 emulation of the kernels' roundings with its planted
@@ -48,7 +48,8 @@ NCU_MI355X = 256
 
 # ------------------------------------------------------------------------------------- the dispatch, restated
 def dispatch(M, N, K, epi, variant, ncu, stagger=HT, sched=0):
-    """hq_gemm_nt_supported, nts_ksplit, half_tile_tail and launch_epi of gemm.hip, restated: which kernel serves
+    """hq_gemm_nt_supported, half_tile_tail and launch of gemm_nt.hip, hq_nt_vs_ksplit of gemm_nt_vs.hip and launch_v3 of
+    gemm_nt_v3.hip, restated: which kernel serves
     (M, N, K, epi) under gemm_set_variant(variant) on ``ncu`` CUs.  bn: what gemm_nt_supported returns."""
     assert N % 128 == 0 and K % 64 == 0 and K >= 64
     big = (256 if N % 256 == 0 else 128) if M % 256 == 0 else 0

@@ -1,4 +1,4 @@
-"""Persistent v3 GEMM tile schedule (gemm.hip, gemm_nt3_kernel): the dynamic per-XCD ticket schedule
+"""Persistent v3 GEMM tile schedule (gemm_nt_v3.hip, gemm_nt3_kernel): the dynamic per-XCD ticket schedule
 must compute exactly what the static round-robin schedule computes — every tile once, same values —
 on repeated launches (the kernel re-zeroes its counters on exit), under a concurrent CU-holding kernel
 on another stream (tiles then land on other workgroups), and inside a captured HIP graph."""

@@ -1,4 +1,4 @@
-"""Out-projection / FFN2 + dropout + residual + LayerNorm with the GEMM's EPI_BDR epilogue (gemm.hip writes
+"""Out-projection / FFN2 + dropout + residual + LayerNorm with the GEMM's EPI_BDR epilogue (gemm_nt*.hip write
 z = dropout(x·Wᵀ + b) + resid, the LayerNorm reads z alone) must be bitwise the unfused pair
 ``linear_fwd`` → ``ln_fwd`` — every GEMM kernel variant (256-row v1 / v2 / persistent v3, 128² tiles for
 M tails), with and without dropout — and match an fp32 reference."""

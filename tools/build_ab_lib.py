@@ -4,7 +4,7 @@ from git revision REV, linked into tools/ab_so/_hq_kernels<ext> (load it with HQ
 AB_DIR=tools/<name> picks another directory; HQ_KERNEL_CFLAGS="-DHQ_EPI_DIAG=1 ..." adds lab defines to THIS build
 only — the production build never reads it).
 
-    python tools/build_ab_lib.py HEAD ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm.hip
+    python tools/build_ab_lib.py HEAD ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm_nt_v3.hip
 
 A file is overlaid whole, so REV must define the same functions in it as the tree does: across the commit that split
 norm.hip (into norm / embed / sort / rowops.hip, the span head into heads.hip) and moved the fp8 quantisers and amax
@@ -13,7 +13,8 @@ link has duplicate or missing hq_* symbols; a subject whose file does not exist 
 cannot be overlaid from before that commit — build that revision whole in a worktree instead.  Likewise across the
 commit that split the fp32 ops file into f32_embed / f32_norm / f32_rowops / f32_attention.hip: from before it, build the whole revision in a worktree
 (AB_DIR still picks where the library goes).  And across the commit that split attention.hip into attention_fwd.hip,
-attention_bwd.hip and include/hq_attn.h: from before it, build the parent whole in a worktree.
+attention_bwd.hip and include/hq_attn.h: from before it, build the parent whole in a worktree.  The same holds across
+the commit that split gemm.hip into gemm_nt.hip, gemm_nt_v1 / _vs / _v2 / _v3.hip and include/hq_gemm_tile.h, hq_gemm_nt.h.
 """
 import os
 import shutil

@@ -2,7 +2,8 @@
 // operands (interleaved rounds in one process, median).  Build + run:
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I ml_recipe_distributed_pytorch_amd/csrc/include \
 //         tools/gemm_lab/gemm_lab.hip -o tools/gemm_lab/gemm_lab && tools/gemm_lab/gemm_lab
-#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm.hip"
+#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm_nt_v1.hip"
+#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm_nt_v2.hip"
 
 #include <algorithm>
 #include <cstdio>
@@ -45,7 +46,7 @@ int main(int argc, char** argv) {
       {"v2-buf-noread", (Kern)gemm_nt2_kernel<0, 10>},
   };
   const int NV = sizeof(vs) / sizeof(vs[0]);
-  const size_t lds = epi_lds(256);
+  const size_t lds = hq_nt_tile_lds(256);
   for (auto& v : vs) CK(hipFuncSetAttribute((const void*)v.k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   for (auto& sh : shapes) {
     const int M = sh[0], N = sh[1], K = sh[2];

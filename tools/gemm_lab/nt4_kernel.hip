@@ -1,6 +1,6 @@
 // bf16 "NT" GEMM, two workgroups per CU:  C[M,N] = A[M,K] · B[N,K]ᵀ (+ fused epilogue)
 //
-// Why a second design next to gemm.hip's 8-wave 256² kernels: those run ONE workgroup per CU, so every
+// Why a second design next to gemm_nt_v2 / _v3.hip's 8-wave 256² kernels: those run ONE workgroup per CU, so every
 // tile's epilogue — bias/GELU/GELU' math on the VALU, the aux-operand loads and 128 KB of stores — runs
 // while the CU's matrix cores sit idle (FFN1 + GELU' at 0.77 PF/s, profiles/r2_gemm_epilogue).  Here a
 // workgroup is 4 waves with a BM × BN tile (2 × 2 waves, each (BM/2) × (BN/2)) and ≤ 80 KB of LDS, so two

@@ -1,10 +1,14 @@
-// GEMM lab: the production NT GEMM (gemm.hip: nt2 / nt3 / vS picked by hq_gemm_nt) against the
+// GEMM lab: the production NT GEMM (gemm_nt*.hip: nt2 / nt3 / vS picked by hq_gemm_nt) against the
 // two-workgroups-per-CU nt4 variants on the BERT-base b256 projection shapes, with their real epilogues,
 // random bf16 operands.  Checks every variant against the production output, then times interleaved
 // rounds in one process (median; cdna_hip_programming.md §5.4 rule 24).  Build + run:
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I ml_recipe_distributed_pytorch_amd/csrc/include \
 //         tools/gemm_lab/nt4_lab.hip -o tools/gemm_lab/nt4_lab && tools/gemm_lab/nt4_lab [M]
-#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm.hip"
+#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm_nt.hip"
+#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm_nt_v1.hip"
+#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm_nt_vs.hip"
+#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm_nt_v2.hip"
+#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm_nt_v3.hip"
 #include "nt4_kernel.hip"
 
 #include <algorithm>

@@ -2,7 +2,7 @@
 // accumulators in the AGPR half of a 512-register budget) against the production v3 kernel.
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I ml_recipe_distributed_pytorch_amd/csrc/include \
 //         tools/gemm_lab/nt5_lab.hip -o tools/gemm_lab/nt5_lab && tools/gemm_lab/nt5_lab
-#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm.hip"
+#include "../../ml_recipe_distributed_pytorch_amd/csrc/kernels/gemm_nt_v3.hip"
 
 #include <algorithm>
 #include <cmath>
