@@ -144,8 +144,8 @@ def attn_fwd(qkv, key_bias, B, L, nh, p, seed, opid, scale):
 
 def deterministic() -> bool:
     """Bitwise run-to-run reproducible kernels wanted: ``torch.use_deterministic_algorithms(True)`` or
-    ``HQ_DETERMINISTIC=1``.  Two ops have a faster order-nondeterministic default that this turns off:
-    the attention backward (the single-kernel backward sums dQ over key slices with LDS float atomics) and the
+    ``HQ_DETERMINISTIC=1``.  One op has a faster order-nondeterministic default that this turns off (the
+    attention backward is atomic-free and ignores the switch; its ``deterministic`` argument is kept for callers): the
     embedding backward's float-atomic scatters — the whole fp32 backward (word, position and >2-type rows), and
     in bf16 / fp8 the position rows of non-default position ids (RoBERTa, ``position_ids=``) and the type rows
     of more than 2 types.  With it on, those gradients are summed over key-sorted runs in a fixed order

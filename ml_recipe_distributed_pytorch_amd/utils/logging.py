@@ -67,8 +67,7 @@ def set_seed(seed=None) -> Optional[int]:
     """Seed python / numpy / torch (CPU and all HIP devices).  ``None`` leaves every generator alone.
 
     Like the reference (modules/utils.py:34-43, ``cudnn.deterministic = True``) a seed also selects the
-    run-to-run reproducible kernels (ops.deterministic): ``HQ_DETERMINISTIC=1`` routes the attention backward
-    to its two-kernel path instead of the single-kernel one with LDS-atomic dQ, and the embedding backward's
+    run-to-run reproducible kernels (ops.deterministic): ``HQ_DETERMINISTIC=1`` routes the embedding backward's
     float-atomic scatters — the whole fp32 backward, and in bf16 / fp8 the position rows of non-default
     position ids (RoBERTa) and the type rows of more than 2 types — to sums over key-sorted runs in a fixed order."""
     if seed is None:

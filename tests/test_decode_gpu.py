@@ -135,11 +135,11 @@ def test_binding_refuses_bad_inputs(cuda):
         ops.qa_decode(*args(), 0)
     a = args()
     a[5] = a[5].long()
-    with pytest.raises(RuntimeError, match="int32"):
+    with pytest.raises(RuntimeError, match="qa_decode: lo has dtype Long, expected Int"):
         ops.qa_decode(*a, 30)
     a = args()
     a[6] = a[6].cpu()
-    with pytest.raises(RuntimeError, match="one device"):
+    with pytest.raises(RuntimeError, match="qa_decode: hi is on cpu, expected cuda"):
         ops.qa_decode(*a, 30)
     a = args()
     a[2] = torch.zeros(3, 9, device=cuda)

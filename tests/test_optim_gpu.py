@@ -450,10 +450,10 @@ def test_bindings_reject_bad_shapes(cuda, kind):
     chunks = _chunk_table().to(cuda)
     n = d["p"].numel()
     short = torch.zeros(n - 4, dtype=torch.bfloat16, device=cuda)
-    with pytest.raises(RuntimeError, match="compute size"):
+    with pytest.raises(RuntimeError, match=rf"{kind}: compute has \d+ elements, expected {n}\b"):
         _launch(k, kind, d, short, chunks, None, 1.0)
     wide = torch.zeros(chunks.shape[0], 3, dtype=torch.int64, device=cuda)
-    with pytest.raises(RuntimeError, match=r"\[n,2\]"):
+    with pytest.raises(RuntimeError, match=rf"{kind}: chunks has sizes \[\d+, 3\], expected \[\d+, 2\]"):
         _launch(k, kind, d, torch.zeros(n, dtype=torch.bfloat16, device=cuda), wide, None, 1.0)
     torch.cuda.synchronize()
     for name in d:
